@@ -2,6 +2,15 @@
 """Benchmark: CSR SpMV effective HBM GB/s on the 300^3 7-point Poisson operand.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 300] [--layout csr|auto]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up the operand, warms up, times the K steps and prints the
+line with the headline alone (value, ms_per_step, the roofline block on the K
+timed launches); --dump-outputs DIR also writes the y of the last timed step.
+Everything else described below — `effective`, `cg`, `cg_gamg`, `host_vec`,
+the flat reads, the Flan stand-ins, roofline.traffic, the CPU baselines,
+result_stable, and at N > 1 the halo forms and the `weak` block — is measured
+only with --full, after the headline and on its own wall budget.
 
 A step is one MatMult (y = A x) of the whole operand, inputs resident in HBM.
 The workload at every N is BASELINE.json configs[1]: 300^3 Poisson CSR (27 M
@@ -76,6 +85,13 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run every other leg (the automatic layout, CG, CG + GAMG, host "
+                        "vectors, flat reads, the Flan stand-ins, PMC traffic, the CPU baselines; N > 1: the halo "
+                        "forms and the weak block), the extra roofline launches and the stability check")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the y of the last timed MatMult as DIR/y.npy (N > 1: "
+                        "DIR/y_rank<r>.npy per rank), float64; above the size cap, a fixed seeded sample of it")
     p.add_argument("--grid", type=int, default=300, help="per-rank grid edge (N^3 rows per rank)")
     p.add_argument("--kernel", default="auto", choices=["auto", "stream", "scalar", "vector"])
     p.add_argument("--geometry", type=int, default=None, help="STREAM geometry 0..11 (default: the library's)")
@@ -772,6 +788,32 @@ def guarded_leg(name, fn, distributed, dev, progress):
 
 METRIC = "CSR SpMV effective HBM GB/s (300^3 7-pt Poisson, fp64 MatMult_SeqAIJ)"
 
+DUMP_BYTES = 32 << 20  # everything one run writes under --dump-outputs, all ranks together
+DUMP_SEED = 1565
+
+
+def dump_indices(m: int, world: int = 1):
+    """Which entries of an m-long y --dump-outputs keeps: all of them (None)
+    when m doubles fit this rank's share of DUMP_BYTES, else a fixed sample
+    of that many, the sorted draws of default_rng(DUMP_SEED): the same m
+    gives the same indices in every run and every build."""
+    keep = DUMP_BYTES // (8 * world)
+    if m <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, m, size=keep))
+
+
+def dump_outputs(directory, y, rank, world):
+    """--dump-outputs: this rank's y of the last timed MatMult (what the
+    caller of mult receives), float64, as y.npy (N > 1: y_rank<r>.npy)."""
+    import torch
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    idx = dump_indices(y.numel(), world)
+    if idx is not None:
+        y = y[torch.from_numpy(idx).to(y.device)]
+    np.save(d / ("y.npy" if world == 1 else f"y_rank{rank}.npy"), y.cpu().numpy().astype(np.float64, copy=False))
+
 
 def slab_row_starts(mpiaij, dims, world):
     """Balanced whole z-planes (DMDA PETSC_DECIDE over z, helper.cpp:31-36
@@ -1109,6 +1151,27 @@ def main():
         dist.all_reduce(el_t, op=dist.ReduceOp.MAX)
     elapsed = float(el_t.item())
     launch_ms = np.array([a.elapsed_time(b) for a, b in ev])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, yd, rank, world)
+
+    # a plain run ends here: the headline from the K timed steps alone (the
+    # roofline block on their K launches), nothing else measured or checked
+    if not args.full:
+        out = headline_line(world=world, dims=dims, nnz_global=nnz_global, K=K, warmup=args.warmup,
+                            elapsed_s=elapsed, launch_us=launch_ms * 1e3, layout_bytes=layout_bytes, info=info,
+                            distributed=distributed, halo=args.halo, x_kind=args.x, planes=planes)
+        out["setup_s"] = round(t_setup, 2)
+        legs.headline_done = True
+        progress("done; writing the line")
+        if distributed:
+            dist.barrier()
+        if rank == 0:
+            out["budget"] = legs.summary()
+            legs.emit(out)
+        legs.disarm()
+        if distributed:
+            dist.destroy_process_group()
+        return
 
     # roofline sample: at least --roofline-reps launches (SURVEY §8d asks
     # for the median of >= 50), the K timed ones plus more if K is smaller

@@ -351,3 +351,50 @@ def test_round6_distributed_records_measure_the_metric(rec, world):
     assert g["its"] == 53 and [lv["rows"] for lv in g["levels"]][:3] == [27_000_000, 2_413_301, 183_694]
     assert set(d["budget"]["legs"]) >= {"cg", "cg_gamg", "cpu_baseline"}
     assert_fracs_at_most_one(d)
+
+
+def test_plain_and_full_flags(bench, monkeypatch):
+    """--full is off by default and --dump-outputs takes a directory; --steps
+    and --warmup are what the timed loop and the line use."""
+    import sys
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "somewhere"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+def test_dump_indices_fixed_sample(bench):
+    """A y that fits the cap is written whole; a larger one as a fixed sample:
+    the same sorted in-range indices at every call, the cap shared by the ranks."""
+    import numpy as np
+    cap = bench.DUMP_BYTES // 8
+    assert bench.DUMP_BYTES <= 64 * 10 ** 6
+    assert bench.dump_indices(cap) is None and bench.dump_indices(100, 8) is None
+    m = 27_000_000
+    i1, i2 = bench.dump_indices(m), bench.dump_indices(m)
+    assert np.array_equal(i1, i2) and len(i1) == cap
+    assert i1.min() >= 0 and i1.max() < m and np.all(np.diff(i1) >= 0)
+    assert len(np.unique(i1 // (m // 300))) == 300  # every z-plane of the 300^3 operand is sampled
+    i8 = bench.dump_indices(m // 8 + 1, 8)
+    assert len(i8) == cap // 8 and i8.max() < m // 8 + 1
+
+
+def test_dump_outputs_files(bench, tmp_path):
+    """y.npy (one rank) / y_rank<r>.npy: float64, the whole vector or the
+    sample of dump_indices, never above the cap."""
+    import numpy as np
+    import torch
+    y = torch.arange(1000, dtype=torch.float64) * 0.5
+    bench.dump_outputs(tmp_path / "a", y, 0, 1)
+    got = np.load(tmp_path / "a" / "y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, y.numpy())
+    m = bench.DUMP_BYTES // 8 + 12345
+    big = torch.arange(m, dtype=torch.float64)
+    bench.dump_outputs(tmp_path / "b", big, 1, 2)
+    f = tmp_path / "b" / "y_rank1.npy"
+    assert sorted(p.name for p in (tmp_path / "b").iterdir()) == ["y_rank1.npy"]
+    got = np.load(f)
+    assert got.dtype == np.float64 and np.array_equal(got, bench.dump_indices(m, 2).astype(np.float64))
+    assert f.stat().st_size <= bench.DUMP_BYTES // 2 + 128

@@ -28,21 +28,21 @@ if [ $TESTS = 1 ]; then
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
       && tail -1 "$OUT/smoke.log" || { tail -20 "$OUT/smoke.log"; exit 1; }
 fi
-timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 echo "bench ok"
-timeout -k 10 600 python -u bench.py --gpus 2 --rehearse-one-gpu --steps 10 --warmup 3 --no-gamg \
+timeout -k 10 600 python -u bench.py --full --gpus 2 --rehearse-one-gpu --steps 10 --warmup 3 --no-gamg \
     > "$OUT/bench_rehearse_n2.json" 2> "$OUT/bench_rehearse_n2.err" \
     && echo "rehearsal n2 ok" || { tail -20 "$OUT/bench_rehearse_n2.err"; exit 1; }
 if [ $N8 = 1 ]; then
-  timeout -k 10 900 python -u bench.py --gpus 8 --rehearse-one-gpu --weak-grid 100 --steps 20 \
+  timeout -k 10 900 python -u bench.py --full --gpus 8 --rehearse-one-gpu --weak-grid 100 --steps 20 \
       --warmup 3 > "$OUT/bench_rehearse_n8.json" 2> "$OUT/bench_rehearse_n8.err" \
       && echo "rehearsal n8 ok" || { tail -20 "$OUT/bench_rehearse_n8.err"; exit 1; }
 fi
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_headline" -o run --output-format csv \
-    -- python3 bench.py --no-cg --no-gamg --no-host-vec --no-flan --no-cpu-baseline > "$OUT/bench_headline_prof.json" \
+    -- python3 bench.py --full --no-cg --no-gamg --no-host-vec --no-flan --no-cpu-baseline > "$OUT/bench_headline_prof.json" \
     2> "$OUT/bench_headline_prof.err" && echo "headline prof ok" || { tail -20 "$OUT/bench_headline_prof.err"; exit 1; }
 if [ $FULLPROF = 1 ]; then
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_bench" -o run --output-format csv \
-      -- python3 bench.py --no-cpu-baseline --no-host-vec > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.err" \
+      -- python3 bench.py --full --no-cpu-baseline --no-host-vec > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.err" \
       && echo "full prof ok" || { tail -20 "$OUT/bench_prof.err"; exit 1; }
 fi

@@ -25,7 +25,7 @@ timeout -k 10 300 python -u tools/tune.py --matrix fem_hex --variants bfauto --r
     && echo "bf fem ok" && grep -h "bitwise\|us_median" "$OUT/bf_fem.jsonl" | tail -7 || exit 1
 timeout -k 10 300 python -u tools/tune.py --matrix skewed --variants overlap --rounds 5 > "$OUT/overlap.jsonl" 2>&1 \
     && echo "overlap ok" && grep us_median "$OUT/overlap.jsonl" | tail -6 || exit 1
-timeout -k 10 300 python -u bench.py --no-cg --no-gamg --no-host-vec --no-flan --no-cpu-baseline --steps 100 \
+timeout -k 10 300 python -u bench.py --full --no-cg --no-gamg --no-host-vec --no-flan --no-cpu-baseline --steps 100 \
     > "$OUT/head.json" 2> "$OUT/head.err" && echo "head ok" || { tail -20 "$OUT/head.err"; exit 1; }
 for r in 1 2; do
   timeout -k 10 200 python -u tools/prof_case.py gamg > "$OUT/gamg_graph_$r.log" 2>&1 || exit 1

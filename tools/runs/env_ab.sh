@@ -9,7 +9,7 @@ for i in $(seq 1 $N); do
   for cfg in "$@"; do
     k=$((k + 1))
     f=$OUT/bench_${i}_$k
-    eval "$cfg timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-host-vec --no-flan --no-pmc \
+    eval "$cfg timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-host-vec --no-flan --no-pmc \
       --no-cpu-baseline" > $f.json 2> $f.err || { tail -20 $f.err; exit 1; }
     python3 - $f.json "$cfg" <<'EOF'
 import json, sys

@@ -24,7 +24,7 @@ for i in $(seq 1 $N); do
     env=""
     [ $lib = base ] && env="AIJHIP_AB=1 AIJHIP_LIB=ablibs/$BASE/libaijhip.so"
     f=$OUT/bench_${i}_$lib
-    eval "$env timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-host-vec --no-flan --no-pmc \
+    eval "$env timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-host-vec --no-flan --no-pmc \
       --no-cpu-baseline" > $f.json 2> $f.err || { tail -20 $f.err; exit 1; }
     summ $f.json "$lib"
   done

@@ -9,7 +9,7 @@
 #                 on one rank)
 #   rehearse_n2 — --gpus 2 --rehearse-one-gpu at 300^3 with CG + GAMG (13.5 M
 #                 rows per rank, host transport)
-#   default    — the driver's N = 1 command (python bench.py)
+#   default    — every leg of the N = 1 bench (python bench.py --full)
 #   rehearse_n8 — the driver's N = 8 line on one GPU: 8 ranks over gloo (host
 #                 transport), the 300^3 strong headline (38/37 planes), a 100^3
 #                 weak block, distributed CG and CG + GAMG
@@ -27,28 +27,28 @@ echo "box GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-unset}"
 if [ "$MODE" = final ]; then
   bash "$ROOT/tools/runs/r06.sh" tests "$TAG" && bash "$ROOT/tools/runs/r06.sh" default "$TAG" || exit 1
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv \
-      -- python3 bench.py --no-pmc > "$OUT/bench_profiled.json" 2> "$OUT/bench_profiled.err" \
+      -- python3 bench.py --full --no-pmc > "$OUT/bench_profiled.json" 2> "$OUT/bench_profiled.err" \
     && echo "profiled bench ok" || { tail -20 "$OUT/bench_profiled.err"; exit 1; }
   exit 0
 fi
 case $MODE in
   default)
-    timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" \
+    timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" \
       && echo "bench ok" || { tail -20 "$OUT/bench.err"; exit 1; }
     ;;
   mpi1)
     AIJHIP_GAMG_DIST=1 timeout -k 10 700 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-        --master-addr 127.0.0.1 --master-port 29517 bench.py --mpi --steps 20 --warmup 5 --wall-budget 600 \
+        --master-addr 127.0.0.1 --master-port 29517 bench.py --full --mpi --steps 20 --warmup 5 --wall-budget 600 \
         > "$OUT/bench_mpi_n1_gamgdist.json" 2> "$OUT/bench_mpi_n1_gamgdist.err" \
       && echo "mpi n1 ok" || { tail -20 "$OUT/bench_mpi_n1_gamgdist.err"; exit 1; }
     ;;
   rehearse_n2)
-    timeout -k 10 1000 python -u bench.py --gpus 2 --rehearse-one-gpu --steps 10 --warmup 3 --wall-budget 900 \
+    timeout -k 10 1000 python -u bench.py --full --gpus 2 --rehearse-one-gpu --steps 10 --warmup 3 --wall-budget 900 \
         > "$OUT/bench_rehearse_n2.json" 2> "$OUT/bench_rehearse_n2.err" \
       && echo "rehearsal n2 ok" || { tail -20 "$OUT/bench_rehearse_n2.err"; exit 1; }
     ;;
   rehearse_n8)
-    timeout -k 10 1000 python -u bench.py --gpus 8 --rehearse-one-gpu --weak-grid 100 --steps 10 --warmup 3 \
+    timeout -k 10 1000 python -u bench.py --full --gpus 8 --rehearse-one-gpu --weak-grid 100 --steps 10 --warmup 3 \
         --wall-budget 900 > "$OUT/bench_rehearse_n8.json" 2> "$OUT/bench_rehearse_n8.err" \
       && echo "rehearsal n8 ok" || { tail -20 "$OUT/bench_rehearse_n8.err"; exit 1; }
     ;;

@@ -22,7 +22,7 @@ for s in ${STEPS:-gamg_mpi parity bench}; do
     vcodes) step vcodes 400 python -u -m pytest tests/test_value_codes_gpu.py tests/test_gamg.py -x -v -m gpu --timeout 200 --timeout-method thread ;;
     patterns) step patterns 400 python -u -m pytest tests/test_row_patterns_gpu.py tests/test_ksp.py tests/test_solver_configs.py -x -v -m gpu --timeout 200 --timeout-method thread ;;
     parity) step parity 300 python -u -m pytest tests/test_gpu_parity.py -x -v -k "gather or geometry" --timeout 200 --timeout-method thread ;;
-    bench) step bench 400 python -u bench.py --no-flan --no-host-vec --no-pmc --steps 20 --warmup 5 ;;
+    bench) step bench 400 python -u bench.py --full --no-flan --no-host-vec --no-pmc --steps 20 --warmup 5 ;;
     tests) step tests 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread ;;
     selfhalo) step selfhalo 300 python -u -m pytest tests/test_rccl_selfhalo_gpu.py tests/test_halo_errors_gpu.py -x -v --timeout 240 --timeout-method thread ;;
     graph) step graph_probe 300 python -u tools/graph_probe.py ;;
