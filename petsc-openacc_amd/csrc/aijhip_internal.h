@@ -219,6 +219,10 @@ struct Plan {
     int32_t pat_dmax = 0;    // largest |column - row| offset in the table (the stencil's plane distance)
     int32_t pat_maxlen = 0;  // longest pattern (entries)
     bool tmpl_diag = false;  // every pattern has the offset 0 (the diagonal)
+    // the pipelined template launch gathers all its slots, a padded one from
+    // the template's first column, an empty template's from x[row]: every
+    // pattern has an entry, or every row index is a column (n >= m)
+    bool tmpl_pipe_ok = false;
     // Tuning::templates: the values of each pattern's entries, indexed like
     // the offsets in d_ptab (n_ptab doubles; the first n_pat unused): MatMult
     // reads neither aj nor aa

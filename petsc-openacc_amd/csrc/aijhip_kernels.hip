@@ -691,6 +691,7 @@ __global__ __launch_bounds__(T) void k_spmv_template(const BlockDesc *__restrict
                                                      const uint8_t *__restrict__ pid, const int32_t *__restrict__ ptab,
                                                      const double *__restrict__ pval, int ntab, int npat, Op op,
                                                      double *dpart, const int *stop) {
+    static_assert(!Op::kXoFromSlot, "no diagonal slot here: x[r] / t[r] from set_diag is the pipelined launch's");
     constexpr int TPT = (kPatTableMax + T - 1) / T;
     __shared__ int32_t tab[kPatTableMax];
     __shared__ double val[kPatTableMax];
@@ -805,8 +806,10 @@ __global__ __launch_bounds__(T) void k_spmv_template(const BlockDesc *__restrict
 // stores only its own row of a live block — the waves of a workgroup do not
 // run in step, so a duplicate's store could land after another wave already
 // stored that row and an in-place MatMultAdd (z = y) read it as its seed. The templates' offsets and values sit in LDS 16-B
-// aligned and zero-padded to kTmplFast (an unused slot gathers x[r] and is
-// not summed). The sum is s = seed, s += value * x in storage order.
+// aligned and padded to kTmplFast (an unused slot gathers the template's first
+// column again, a column the row reads, and is not summed; an empty template
+// has none and gathers x[r]: Plan::tmpl_pipe_ok). The sum is s = seed,
+// s += value * x in storage order.
 constexpr int kTmplFast = 8;
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 // F: the gather slots a row takes (7 where every template has at most 7
@@ -914,7 +917,7 @@ __global__ __launch_bounds__(T) void k_spmv_template_pipe(const BlockDesc *__res
         const int e = t + i * T, pp = e / kTmplFast, j = e % kTmplFast;
         if (pp < npat) {
             const int32_t pm = ptab[pp], st = pm & 0xffff, n = pm >> 16;
-            off8[e] = j < n ? ptab[st + j] : 0;
+            off8[e] = j < n ? ptab[st + j] : n > 0 ? ptab[st] : 0;
             val8[e] = j < n ? pval[st + j] : 0.0;
         }
     }
@@ -987,30 +990,39 @@ static void launch_template_pipe(const aijhip_mat &A, const Op &op, double *dpar
     hipLaunchKernelGGL((k_spmv_template_pipe<TP, F, Op>), dim3(g), dim3(TP), 0, s, P.d_tblocks, P.n_blocks, P.d_pid,
                        P.d_ptab, P.d_pval, P.n_ptab, P.n_pat, op, dpart, stop);
 }
+// The pipelined launch gathers every slot of a row: a padded slot repeats the
+// template's first column, an empty template has none and gathers x[row]
+// (Plan::tmpl_pipe_ok: no empty template, or every row index is a column)
+static bool template_pipelined(const Plan &P) { return P.pat_maxlen <= kTmplFast && P.tmpl_pipe_ok; }
 template <class Op>
-static void launch_template(const aijhip_mat &A, const Op &op, double *dpart, hipStream_t s, const int *stop) {
+static hipError_t launch_template(const aijhip_mat &A, const Op &op, double *dpart, hipStream_t s, const int *stop) {
     const Plan &P = A.plan;
     static_assert(kStreamGeoms[6].rows == kTmplThreads * kTmplRows, "a block's rows = the lanes x kTmplRows");
-    if (P.pat_maxlen <= kTmplFast) {
+    if (template_pipelined(P)) {
         // persistent: as many workgroups as fit on the device at once (the
         // kernel's registers decide), a multiple of 8 for the XCD chunks
         constexpr int TP = kStreamGeoms[6].threads;
         if (P.pat_maxlen <= 7) launch_template_pipe<TP, 7>(A, op, dpart, s, stop);
         else launch_template_pipe<TP, kTmplFast>(A, op, dpart, s, stop);
-        return;
+        return hipSuccess;
     }
-    hipLaunchKernelGGL((k_spmv_template<kTmplThreads, kTmplRows, Op>), dim3(template_grid(A, P.n_blocks)),
-                       dim3(kTmplThreads), 0, s, P.d_blocks, P.n_blocks, 1, P.d_pid, P.d_ptab, P.d_pval, P.n_ptab,
-                       P.n_pat, op, dpart, stop);
+    if constexpr (Op::kXoFromSlot) {
+        return hipErrorInvalidValue;  // the diagonal slot exists in the pipelined launch only: the callers' choice
+    } else {
+        hipLaunchKernelGGL((k_spmv_template<kTmplThreads, kTmplRows, Op>), dim3(template_grid(A, P.n_blocks)),
+                           dim3(kTmplThreads), 0, s, P.d_blocks, P.n_blocks, 1, P.d_pid, P.d_ptab, P.d_pval, P.n_ptab,
+                           P.n_pat, op, dpart, stop);
+        return hipSuccess;
+    }
 }
 // MatMult / MatMultAdd: the dot as a compile-time choice (OpMultT)
 template <bool ADD>
-static void launch_template(const aijhip_mat &A, const OpMult<ADD> &op, double *dpart, hipStream_t s,
-                            const int *stop) {
+static hipError_t launch_template(const aijhip_mat &A, const OpMult<ADD> &op, double *dpart, hipStream_t s,
+                                  const int *stop) {
     const Plan &P = A.plan;
-    if (op.dot && P.tmpl_diag && P.pat_maxlen <= kTmplFast) launch_template(A, OpMultT<ADD, true, true>{op}, dpart, s, stop);
-    else if (op.dot) launch_template(A, OpMultT<ADD, true>{op}, dpart, s, stop);
-    else launch_template(A, OpMultT<ADD, false>{op}, dpart, s, stop);
+    if (op.dot && P.tmpl_diag && template_pipelined(P)) return launch_template(A, OpMultT<ADD, true, true>{op}, dpart, s, stop);
+    if (op.dot) return launch_template(A, OpMultT<ADD, true>{op}, dpart, s, stop);
+    return launch_template(A, OpMultT<ADD, false>{op}, dpart, s, stop);
 }
 
 // Segments of long rows: tree-reduced partial sums. (Round 5: lane t taking
@@ -1671,6 +1683,7 @@ hipError_t build_row_patterns(const aijhip_mat &A, Plan &P, bool *ok, bool value
         for (int j = 0; j < len[p]; ++j) has = has || off[(size_t)p * kPatTableMax + j] == 0;
         P.tmpl_diag = P.tmpl_diag && has;
     }
+    P.tmpl_pipe_ok = *std::min_element(len.begin(), len.end()) > 0 || A.n >= A.m;
     auto drop = [&]() {
         hipFree(P.d_pid);
         hipFree(P.d_ptab);
@@ -1994,7 +2007,7 @@ static void stream_dispatch(const aijhip_mat &A, const Plan &P, const RowList &L
         if (P.d_pid && !L.ridx) {
 #define AIJHIP_PT(ADD)                                                                                        \
     if (P.d_pval)                                                                                             \
-        launch_template(A, OpMult<ADD>{x, z, y, dpart != nullptr}, dpart, s, stop);                           \
+        (void)launch_template(A, OpMult<ADD>{x, z, y, dpart != nullptr}, dpart, s, stop);                     \
     else                                                                                                      \
         hipLaunchKernelGGL((k_spmv_pattern<T, CAP, OpMult<ADD>>), dim3(P.n_blocks), dim3(T), 0, s, P.d_blocks, \
                            L.rai, P.d_pid, P.d_ptab, P.n_ptab, P.n_pat, A.d_aa,                                 \
@@ -2161,8 +2174,8 @@ static hipError_t launch_stream_op(const aijhip_mat &A, const Op &op, double *dp
     const int ex = exact < 0 ? (int)P.tune.exact : exact;
     if (P.d_pid && P.d_pval) {  // row templates (planned at geometry 6)
         if (P.tune.geom != 6) return hipErrorInvalidValue;
-        launch_template(A, op, dpart, s, stop);
-        return hipGetLastError();
+        const hipError_t e = launch_template(A, op, dpart, s, stop);
+        return e != hipSuccess ? e : hipGetLastError();
     }
     if (P.d_pid) {  // row patterns (planned at geometry 6)
         if (P.tune.geom != 6) return hipErrorInvalidValue;
@@ -2241,7 +2254,7 @@ hipError_t launch_mg_resid(const aijhip_mat &A, const double *x, const double *b
 hipError_t launch_mg_post(const aijhip_mat &A, const double *t, const double *b, const double *dinv, double *x,
                           double *dpart, hipStream_t s, bool nt, const int *stop, const double *tdinv) {
     if (tdinv && A.plan.d_pid && A.plan.d_pval) {  // row templates: D^-1 per template
-        if (A.plan.tmpl_diag && A.plan.pat_maxlen <= kTmplFast)  // the pipelined launch: t[r] from the diagonal slot
+        if (A.plan.tmpl_diag && template_pipelined(A.plan))  // the pipelined launch: t[r] from the diagonal slot
             return launch_stream_op(A, OpMgPost<true, true, true>{t, b, dinv, x, dpart != nullptr, A.plan.d_pid, tdinv},
                                     dpart, s, -1, stop);
         return launch_stream_op(A, OpMgPost<true, true>{t, b, dinv, x, dpart != nullptr, A.plan.d_pid, tdinv}, dpart,

@@ -291,3 +291,170 @@ def test_cg_and_gamg_with_patterns_bitwise(pkg, dev):
             assert out[0, 0][0] == out[key][0]
             assert_bits(out[0, 0][1], out[key][1])
             assert_bits(out[0, 0][2], out[key][2])
+
+
+def x_in_row_sized_buffer(x, m, dev):
+    """x as the first len(x) entries of a device buffer of max(m, len(x))
+    doubles whose tail is NaN: a gather at a row index past the columns (a
+    padded template slot) stays inside the buffer, and nothing that is
+    summed may come from there."""
+    buf = torch.full((max(m, len(x)),), np.nan, dtype=torch.float64, device=dev)
+    buf[:len(x)] = to_dev(x, dev)
+    return buf[:len(x)]
+
+
+def assert_products_bitwise(pkg, dev, coracle, ai, aj, aa, n, x, z, expect):
+    """MatMult, MatMultAdd and in-place MatMultAdd equal the oracle bit for
+    bit on the requested layout and with templates off; `expect` = the
+    (row_templates, row_patterns) that info() must report first."""
+    m = len(ai) - 1
+    y_ref = coracle.matmult(ai, aj, aa, x)
+    w_ref = coracle.matmult_add(ai, aj, aa, x, z)
+    with pkg.SeqAIJHIP(ai, aj, aa, ncols=n, row_patterns=1) as A:
+        info = A.info()
+        assert (info["row_templates"], info["row_patterns"]) == expect
+        xd, zd = x_in_row_sized_buffer(x, m, dev), to_dev(z, dev)
+        for templates in (1, 0):
+            if not templates:
+                A.set_option("row_templates", 0)
+                assert A.info()["row_templates"] == 0
+            y = torch.full((m,), np.nan, dtype=torch.float64, device=dev)
+            w = torch.full((m,), np.nan, dtype=torch.float64, device=dev)
+            wi = zd.clone()
+            A.mult(xd, y)
+            A.mult_add(xd, zd, w)
+            A.mult_add(xd, wi, wi)
+            torch.cuda.synchronize()
+            assert_bits(y.cpu().numpy(), y_ref)
+            assert_bits(w.cpu().numpy(), w_ref)
+            assert_bits(wi.cpu().numpy(), w_ref)
+
+
+RECT_VARIANTS = (((), ()), ((0,), (0.5,)), ((0, 2), (-1.0, 2.0)), ((0, 1, 2), (0.25, -1.0, 0.5)),
+                 ((0, 1, 3), (2.0, 0.5, -0.25)))
+
+
+def tall_rect_csr(m, n, rng):
+    """m x n, m >> n: row r takes one of RECT_VARIANTS (none to three
+    entries, about 1 in 20 rows none) at column r % (n - 3) + offset, so the
+    rows of each run of n - 3 share their column - row offsets and the
+    operand has ~ 4 m / (n - 3) + 1 templates."""
+    pick = np.where(rng.random(m) < 0.05, 0, rng.integers(1, len(RECT_VARIANTS), m))
+    pick[[n + 3, m - 1]] = 0  # empty rows whose index is no column
+    cols = [np.array(RECT_VARIANTS[p][0], dtype=np.int64) + r % (n - 3) for r, p in enumerate(pick)]
+    vals = [np.array(RECT_VARIANTS[p][1]) for p in pick]
+    ai = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int32)
+    return ai, np.concatenate(cols).astype(np.int32), np.concatenate(vals)
+
+
+def test_templates_rectangular_with_empty_rows(pkg, dev, coracle):
+    """Fewer columns than rows (1537 x 40), some rows empty, some of those
+    past the last column: the pipelined launch's padded slots gather the
+    template's own first column, and an empty template (which has none)
+    sends the operand to the 2-rows-per-lane kernel, whose gathers are per
+    entry. x sits in a buffer of m doubles with a NaN tail: every gather
+    stays inside it and no product depends on one past x."""
+    m, n = 1537, 40
+    rng = np.random.default_rng(1537)
+    ai, aj, aa = tall_rect_csr(m, n, rng)
+    lens = np.diff(ai)
+    assert aj.max() < n and lens.max() == 3
+    assert 0.03 * m < (lens == 0).sum() < 0.08 * m and (np.flatnonzero(lens == 0) >= n).any()
+    rows = np.repeat(np.arange(m), lens)
+    temps = {tuple(aj[ai[i]:ai[i + 1]] - rows[ai[i]:ai[i + 1]]) + tuple(aa[ai[i]:ai[i + 1]].view(np.uint64))
+             for i in range(m)}
+    assert len(temps) <= 256 and len(temps) + sum(len(t) // 2 for t in temps) <= 1024
+    x, z = rng.uniform(-1, 1, n), rng.uniform(-1, 1, m)
+    assert_products_bitwise(pkg, dev, coracle, ai, aj, aa, n, x, z, (1, len(temps)))
+
+
+def test_templates_wide_rectangular_one_short_block(pkg, dev, coracle):
+    """The transposed shape, 40 x 1537: one row block of fewer than 64 rows,
+    every row its own template (none to three entries anywhere in the
+    columns), empty rows included — with at least as many columns as rows
+    the pipelined launch keeps them (their slots gather x[row])."""
+    m, n = 40, 1537
+    rng = np.random.default_rng(40)
+    palette = np.array([0.5, -1.0, 2.0, 0.25])
+    cols = [np.unique(rng.integers(0, n, rng.integers(0, 4))) for _ in range(m)]
+    cols[7], cols[39] = cols[7][:0], cols[39][:0]
+    vals = [palette[rng.integers(0, 4, len(c))] for c in cols]
+    ai = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int32)
+    aj, aa = np.concatenate(cols).astype(np.int32), np.concatenate(vals)
+    lens = np.diff(ai)
+    assert lens.max() == 3 and (lens == 0).sum() >= 2
+    ntemps = len({tuple(c - r) + tuple(v) for r, (c, v) in enumerate(zip(cols, vals))})
+    x, z = rng.uniform(-1, 1, n), rng.uniform(-1, 1, m)
+    assert_products_bitwise(pkg, dev, coracle, ai, aj, aa, n, x, z, (1, ntemps))
+
+
+def capacity_csr(m, ntrip, long_row=None):
+    """m x (m + 2): row i holds columns i, i + 1, i + 2 with value triplet
+    (7 i + 3) % ntrip of a palette of distinct triplets — one offset list,
+    ntrip templates, each of them in every run of ntrip rows. long_row: that
+    row gets a fourth entry at i + 3."""
+    t = (7 * np.arange(m) + 3) % ntrip
+    pal = np.stack([0.5 + np.arange(ntrip) / 256.0, -1.0 - np.arange(ntrip) / 512.0, np.full(ntrip, 0.25)], axis=1)
+    cols = [np.arange(i, i + 3) for i in range(m)]
+    vals = [pal[k] for k in t]
+    if long_row is not None:
+        cols[long_row] = np.arange(long_row, long_row + 4)
+        vals[long_row] = np.array([3.0, -3.0, 1.5, 0.125])
+    ai = np.concatenate([[0], np.cumsum([len(c) for c in cols])]).astype(np.int32)
+    return ai, np.concatenate(cols).astype(np.int32), np.concatenate(vals)
+
+
+@pytest.mark.parametrize("case,ntrip,long_row,templates", [("a", 256, None, 1), ("b", 257, None, 0),
+                                                           ("c", 255, 1000, 0)])
+def test_template_table_capacity(pkg, dev, coracle, case, ntrip, long_row, templates):
+    """The plan's limits, at them and one past: 256 templates (an 8-bit id)
+    and 1024 table words (a word and the offsets per template).
+    a: 256 templates of 3 entries = 256 + 768 = 1024 words: templates, and
+       the last id, 255, on rows of every block (each run of 256 rows holds
+       every template), the last block's included;
+    b: 257 templates: none; the one offset list stays as a row pattern;
+    c: 255 templates of 3 entries and one of 4 = 256 + 769 = 1025 words: none;
+       the two offset lists stay as row patterns (info() reports 2).
+    MatMult and MatMultAdd bitwise the oracle's in all three."""
+    m = 4096
+    ai, aj, aa = capacity_csr(m, ntrip, long_row)
+    trips = {tuple(aa[ai[i]:ai[i + 1]].view(np.uint64)) for i in range(m)}
+    assert len(trips) == ntrip + (long_row is not None)
+    assert len({tuple(aa[ai[i]:ai[i + 1]].view(np.uint64)) for i in range(m - 256, m)}) >= min(ntrip, 255)
+    words = len(trips) + sum(len(t) for t in trips)
+    assert (words <= 1024 and len(trips) <= 256) == bool(templates)
+    x, z = pkg.splitmix_uniform(m + 2, 11), pkg.splitmix_uniform(m, 12)
+    with pkg.SeqAIJHIP(ai, aj, aa, ncols=m + 2, row_patterns=1) as A:
+        info = A.info()
+        print(f"case {case}: row_templates {info['row_templates']}, row_patterns {info['row_patterns']}")
+        assert info["row_templates"] == templates
+        if case == "a":
+            assert info["row_patterns"] == 256
+        if case == "b":
+            assert info["row_patterns"] == 1
+        y, w = products(A, x, z, dev)
+        assert_bits(y, coracle.matmult(ai, aj, aa, x))
+        assert_bits(w, coracle.matmult_add(ai, aj, aa, x, z))
+
+
+def test_templates_keep_the_sign_of_a_stored_zero(pkg, dev, coracle):
+    """Rows that differ only in the sign of a stored 0.0 are two templates
+    (the templates hash the value bits): with z = -0.0 and x > 0 MatMultAdd
+    gives -0.0 + 0.0 x = +0.0 on the one and -0.0 + (-0.0) x = -0.0 on the
+    other, the oracle's bits."""
+    m = 700
+    ai = np.arange(m + 1, dtype=np.int32)
+    aj = np.arange(m, dtype=np.int32)
+    aa = np.where(np.arange(m) % 3 == 1, -0.0, 0.0)
+    x, z = np.random.default_rng(0).uniform(0.5, 1.0, m), np.full(m, -0.0)
+    ref = coracle.matmult_add(ai, aj, aa, x, z)
+    assert np.array_equal(np.signbit(ref), np.arange(m) % 3 == 1)
+    with pkg.SeqAIJHIP(ai, aj, aa, row_patterns=1) as A:
+        info = A.info()
+        assert (info["row_templates"], info["row_patterns"]) == (1, 2)
+        _, w = products(A, x, z, dev)
+        assert_bits(w, ref)
+        wi = to_dev(z, dev)
+        A.mult_add(to_dev(x, dev), wi, wi)
+        torch.cuda.synchronize()
+        assert_bits(wi.cpu().numpy(), ref)
