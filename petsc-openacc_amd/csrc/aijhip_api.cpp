@@ -898,21 +898,25 @@ int64_t mult_layout_bytes(const aijhip_mat &A) {
     const int64_t rows = A.compressed ? (4 * ((int64_t)A.n_crow + 1) + 4 * (int64_t)A.n_crow) : 4 * (m + 1);
     const int64_t vec = 8 * n + 8 * m;
     if (P.kernel != AIJHIP_KERNEL_STREAM) return 12 * nz + rows + vec;
-    if (P.d_pid && P.d_pval)  // row templates: a template id per row, the table (offsets and values)
+    const StreamLayout D = stream_layout(A, StreamAsk::Mult);
+    if (D.kind == StreamLayout::kTemplate)  // a template id per row, the table (offsets and values)
         return m + 12 * (int64_t)P.n_ptab + vec;
-    if (P.d_pid)  // aa, ai, a pattern id per row and the offset table
+    if (D.kind == StreamLayout::kPattern)  // aa, ai, a pattern id per row and the offset table
         return 8 * nz + rows + m + 4 * (int64_t)P.n_ptab + vec;
-    if (P.d_code)  // coded entries 10 B, blocks launched from aj 12 B, the dictionaries
-        return 10 * (nz - P.nz_wide) + 12 * P.nz_wide + rows + vec + 4 * P.n_cmeta;
-    if (P.d_sidx && P.d_svcode)  // packed columns and slots, value codes (6 B per entry), the dictionary
-        return 6 * nz + rows + vec + 4 * (int64_t)P.n_blocks + 8 * (int64_t)P.n_vdict;
-    if (P.d_vcode && !P.d_sslot)  // aj and value codes (6 B per entry), the dictionary
-        return 6 * nz + rows + vec + 8 * (int64_t)P.n_vdict;
-    if (P.d_sidx)  // packed columns and slots (4 B per entry), sorted values, block bases
-        return 12 * nz + rows + vec + 4 * (int64_t)(P.n_blocks - P.n_wblocks);
-    if (P.d_sslot)  // sorted 32-bit columns + sorted values + 16-bit slots
-        return 14 * nz + rows + vec;
-    return 12 * nz + rows + vec;
+    switch (D.main.mode) {
+        case kStreamCodes:
+        case kStreamCodesNT:  // coded entries 10 B, blocks launched from aj 12 B, the dictionaries
+            return 10 * (nz - P.nz_wide) + 12 * P.nz_wide + rows + vec + 4 * P.n_cmeta;
+        case kStreamPackedValueCodes:  // packed columns and slots, value codes (6 B per entry), the dictionary
+            return 6 * nz + rows + vec + 4 * (int64_t)P.n_blocks + 8 * (int64_t)P.n_vdict;
+        case kStreamValueCodes:  // aj and value codes (6 B per entry), the dictionary
+            return 6 * nz + rows + vec + 8 * (int64_t)P.n_vdict;
+        case kStreamPacked:  // packed columns and slots (4 B per entry), sorted values, block bases
+            return 12 * nz + rows + vec + 4 * (int64_t)(P.n_blocks - P.n_wblocks);
+        case kStreamSorted32:  // sorted 32-bit columns + sorted values + 16-bit slots
+            return 14 * nz + rows + vec;
+        default: return 12 * nz + rows + vec;
+    }
 }
 }  // namespace aijhip
 

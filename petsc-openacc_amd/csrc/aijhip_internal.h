@@ -238,6 +238,50 @@ struct Plan {
     HostPipe *hpipe = nullptr;  // built on the first host-vector MatMult
 };
 
+// k_spmv_stream's MODE, a sum of these flags (stream_block documents what each does to the
+// kernel). The template parameter is an int: its values are part of the kernels' names.
+constexpr int kModeNT = 1;            // non-temporal matrix loads
+constexpr int kModeSorted32 = 8;      // gather-ordered blocks: 32-bit sorted columns, 16-bit slots (Plan::d_saj)
+constexpr int kModePacked = 16;       // gather-ordered blocks: packed columns and slots (Plan::d_sidx)
+constexpr int kModeCodes = 32;        // column codes (Plan::d_code)
+constexpr int kModeBranchFree = 64;   // branch-free phase 1
+constexpr int kModeValueCodes = 128;  // value codes in aa's place (Plan::d_vcode / d_svcode)
+// ... and the sums that are launched (stream_layout chooses among them)
+constexpr int kStreamPlain = 0;
+constexpr int kStreamNT = kModeNT;
+constexpr int kStreamSorted32 = kModeSorted32;
+constexpr int kStreamWide = kModeBranchFree | kModeNT;  // the wide blocks of a split plan, from aj / aa
+constexpr int kStreamPacked = kModeBranchFree | kModePacked;
+constexpr int kStreamCodes = kModeBranchFree | kModeCodes;
+constexpr int kStreamCodesNT = kStreamCodes | kModeNT;
+constexpr int kStreamValueCodes = kModeValueCodes;
+constexpr int kStreamPackedValueCodes = kStreamPacked | kModeValueCodes;
+constexpr int kStreamModes[] = {kStreamPlain,  kStreamNT,      kStreamSorted32,   kStreamWide,            kStreamPacked,
+                                kStreamCodes,  kStreamCodesNT, kStreamValueCodes, kStreamPackedValueCodes};
+constexpr int kNumStreamModes = sizeof(kStreamModes) / sizeof(kStreamModes[0]);
+
+// One k_spmv_stream launch: the row blocks, the kernel's MODE and the arrays
+// it reads in aj's / aa's place. n_blocks == 0: no launch.
+struct StreamPart {
+    const BlockDesc *blocks = nullptr;
+    int32_t n_blocks = 0;
+    int mode = kStreamPlain;
+    const int32_t *aj = nullptr;       // aj, d_saj, d_sidx (packed words) or d_code (16-bit codes)
+    const double *aa = nullptr;        // aa, d_saa, or d_vcode / d_svcode (16-bit value codes)
+    const uint16_t *sslot = nullptr;   // kModeSorted32: the products' slots
+    const int32_t *aux = nullptr;      // kModePacked: d_sbase; kModeCodes: d_cmeta
+    const double *vdict = nullptr;     // kModeValueCodes: the dictionary
+    int32_t n_vdict = 0;
+};
+// What serves a plan's row blocks for one caller (stream_layout)
+struct StreamLayout {
+    enum Kind { kStream, kPattern, kTemplate, kInvalid } kind = kStream;
+    StreamPart main;  // kStream: all blocks, or the narrow / coded ones of a split plan
+    StreamPart wide;  // ... and then its wide blocks (kStreamWide from aj / aa), else empty
+};
+// Who asks: MatMult / MatMultAdd, the same with the CG's dot partials, or a fused V-cycle / set-up op
+enum class StreamAsk { Mult, MultDot, Fused };
+
 }  // namespace aijhip
 
 struct aijhip_mat {
@@ -303,10 +347,12 @@ hipError_t launch_dinv_mult(const aijhip_mat &A, const double *dinv, const doubl
 hipError_t launch_mult_exact(const aijhip_mat &A, const double *x, double *y, hipStream_t s);
 // r = b - A x on a STREAM plan (residual in the SpMV epilogue).
 hipError_t launch_mg_resid(const aijhip_mat &A, const double *x, const double *b, double *r, hipStream_t s,
-                           bool nt, const int *stop = nullptr);
+                           const int *stop = nullptr);
 hipError_t launch_mg_post(const aijhip_mat &A, const double *t, const double *b, const double *dinv, double *x,
-                          double *dpart, hipStream_t s, bool nt, const int *stop = nullptr,
-                          const double *tdinv = nullptr);
+                          double *dpart, hipStream_t s, const int *stop = nullptr, const double *tdinv = nullptr);
+// The kernel, mode and arrays that serve A's STREAM row blocks for `ask`: the
+// one place that decides it (the launchers and mult_layout_bytes read it).
+StreamLayout stream_layout(const aijhip_mat &A, StreamAsk ask);
 // Dispatch y = A x (or w = z + A x) through the handle's plan. stop: a device
 // flag (CG's `done`); STREAM row blocks return at once once it is set.
 hipError_t launch_mult(const aijhip_mat &A, const double *x, const double *z, double *y,

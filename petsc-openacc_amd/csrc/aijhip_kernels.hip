@@ -33,6 +33,8 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "aijhip_internal.h"
@@ -278,7 +280,8 @@ __device__ __forceinline__ double row_sum_seq(const double *p, int32_t n, double
 // One STREAM row block b of blk[0, nblk) by the T lanes of the calling
 // workgroup; prod (CAP doubles) and cdict (kCodeDictMax ints, column codes
 // only) are the workgroup's LDS.
-// NTMODE bit 0: non-temporal matrix loads (scattered long-row operands).
+// NTMODE: a sum of the kMode* flags (aijhip_internal.h), each explained where
+// it is tested below; kModeNT is for scattered long-row operands.
 template <int T, int CAP, int RPT, bool CROW, int NTMODE, class Op>
 __device__ __forceinline__ void stream_block(
     const int b, const BlockDesc *__restrict__ blk, int nblk, int exact,
@@ -286,22 +289,22 @@ __device__ __forceinline__ void stream_block(
     const double *__restrict__ aa, const Op &op, double *dpart, const int *stop, const uint16_t *__restrict__ sslot,
     const int32_t *__restrict__ sbase, double *prod, int32_t *cdict, const double *__restrict__ vdict, int nvd,
     double *vlds) {
-    constexpr bool NT = (NTMODE & 1) != 0;
+    constexpr bool NT = (NTMODE & kModeNT) != 0;
     // bit 3: gather-ordered blocks (Plan::d_saj/d_saa): aj/aa hold each
     // block's entries sorted by column, sslot their positions in the block,
     // where the products go; the row sums below read them in storage order
-    constexpr bool SORTED = (NTMODE & 8) != 0;
+    constexpr bool SORTED = (NTMODE & kModeSorted32) != 0;
     // bit 4: the same with each entry's column (relative to the block's
     // first, sbase[b]; 20 bits) and slot (12 bits) packed in one word in
     // aj's place (k_pack_gather_order): one 8-B load per pair as in CSR, 12
     // bytes per entry like the original arrays
-    constexpr bool S16 = (NTMODE & 16) != 0;
+    constexpr bool S16 = (NTMODE & kModePacked) != 0;
     // bit 5: column codes (Plan::d_code, full-row lists only): aj holds one
     // 16-bit code per entry, (row - row0) << b | index into the block's
     // dictionary of column - row offsets; sbase holds per block {dictionary
     // start, size} and then the dictionaries. 10 bytes per entry instead of
     // 12; the products, their slots and the sums are the plain kernel's
-    constexpr bool CODES = (NTMODE & 32) != 0;
+    constexpr bool CODES = (NTMODE & kModeCodes) != 0;
     static_assert(!(CODES && (S16 || SORTED || CROW)), "column codes: plain full-row form only");
     // bit 6: phase 1 without branches: every lane loads its pairs (lanes past
     // the block re-read the block's last pair) and gathers them, so the
@@ -310,7 +313,7 @@ __device__ __forceinline__ void stream_block(
     // per-pair `if`s to branches, and at each join the gathers wait for every
     // earlier load, their own predecessors included (vmcnt(0) per pair: four
     // gather round trips per lane instead of one).
-    constexpr bool BF = (NTMODE & 64) != 0;
+    constexpr bool BF = (NTMODE & kModeBranchFree) != 0;
     static_assert(!(BF && SORTED), "branch-free phase 1: plain, coded and 16-bit gather-ordered forms");
     // bit 7: value codes (Plan::d_vcode, set-up operators with few distinct
     // values, e.g. GAMG's finest P and P^T): `aa` holds a 16-bit index per
@@ -318,7 +321,7 @@ __device__ __forceinline__ void stream_block(
     // (nvd <= kVDictMax values, staged in LDS; decoded after the gathers are
     // issued): 6 bytes per entry read instead of 12 with aj or the packed
     // columns; the products are the same bits
-    constexpr bool VC = (NTMODE & 128) != 0;
+    constexpr bool VC = (NTMODE & kModeValueCodes) != 0;
     static_assert(!VC || (!CODES && !SORTED && (BF || !S16)),
                   "value codes: the plain (predicated or branch-free) or 16-bit gather-ordered forms");
     constexpr int ITERS = (CAP + 1 + 2 * T - 1) / (2 * T);
@@ -583,8 +586,8 @@ __global__ __launch_bounds__(T) void k_spmv_stream(
     const double *__restrict__ aa, Op op, double *dpart, const int *stop, const uint16_t *__restrict__ sslot,
     const int32_t *__restrict__ sbase, const double *__restrict__ vdict = nullptr, int nvd = 0) {
     __shared__ double prod[CAP];
-    __shared__ int32_t cdict[(NTMODE & 32) ? kCodeDictMax : 1];
-    __shared__ double vlds[(NTMODE & 128) ? kVDictMax : 1];
+    __shared__ int32_t cdict[(NTMODE & kModeCodes) ? kCodeDictMax : 1];
+    __shared__ double vlds[(NTMODE & kModeValueCodes) ? kVDictMax : 1];
     stream_block<T, CAP, RPT, CROW, NTMODE, Op>((int)blockIdx.x, blk, nblk, exact, rai, ridx, aj, aa, op, dpart, stop,
                                                 sslot, sbase, prod, cdict, vdict, nvd, vlds);
 }
@@ -1984,128 +1987,66 @@ static hipError_t compressed_prologue(const aijhip_mat &A, const double *z, doub
     return hipSuccess;
 }
 
-// The wide blocks (few long rows of scattered columns each, split from the
-// narrow ones) on the branch-free phase 1 with non-temporal matrix loads:
-// with the predicated form each lane's eight scattered gathers waited on one
-// another (vmcnt(0) per pair), and a launch of a few dozen such blocks is
-// one block's latency — 29 us of the skewed stand-in's serial 331 us
-// (round 5, profiles/r05/x)
-constexpr int kWideMode = 64 | 1;
-
-template <int T, int CAP, int RPT>
-static void stream_dispatch(const aijhip_mat &A, const Plan &P, const RowList &L, const double *x,
-                            const double *z, double *y, bool add, hipStream_t s, double *dpart,
-                            const int *stop, hipStream_t sw) {  // sw: the wide blocks' stream
-    constexpr bool kGeom6 = T == kStreamGeoms[6].threads && CAP == kStreamGeoms[6].nnz_cap && RPT == 1;
-#define AIJHIP_SL(ADD, CROW, NT)                                                                             \
-    hipLaunchKernelGGL((k_spmv_stream<T, CAP, RPT, CROW, NT, OpMult<ADD>>), dim3(P.n_blocks), dim3(T), 0, s, \
-                       P.d_blocks, P.n_blocks, (int)P.tune.exact, L.rai, L.ridx, A.d_aj, A.d_aa,             \
-                       OpMult<ADD>{x, z, y, dpart != nullptr}, dpart, stop, nullptr, nullptr);       \
-    return
-    // Row patterns (Plan::d_pid; geometry 6, full-row lists, short rows)
-    if constexpr (kGeom6) {
-        if (P.d_pid && !L.ridx) {
-#define AIJHIP_PT(ADD)                                                                                        \
-    if (P.d_pval)                                                                                             \
-        (void)launch_template(A, OpMult<ADD>{x, z, y, dpart != nullptr}, dpart, s, stop);                     \
-    else                                                                                                      \
-        hipLaunchKernelGGL((k_spmv_pattern<T, CAP, OpMult<ADD>>), dim3(P.n_blocks), dim3(T), 0, s, P.d_blocks, \
-                           L.rai, P.d_pid, P.d_ptab, P.n_ptab, P.n_pat, A.d_aa,                                 \
-                           OpMult<ADD>{x, z, y, dpart != nullptr}, dpart, stop);                                \
-    return
-            if (add) { AIJHIP_PT(true); }
-            AIJHIP_PT(false);
-#undef AIJHIP_PT
-        }
+// Which kernel, mode and arrays serve the plan's row blocks. The first row
+// that applies decides; g6 = geometry 6, crow = compressed rows, split =
+// n_wblocks > 0 (some blocks narrow / coded, the others wide, from aj / aa).
+//
+//   the plan has          Mult               MultDot            Fused
+//   d_pid, d_pval         template  [g6, !crow, both]           template [g6, else invalid]
+//   d_pid                 pattern   [g6, !crow, both]           pattern  [g6, else invalid]
+//   d_code [g6, !crow]    Codes(NT) + Wide   Codes(NT) [!split] Codes [!split], never NT
+//   d_sidx, d_svcode      PackedValueCodes   the same  [!split] -
+//     [g6, !crow]           + Wide
+//   d_sidx                Packed + Wide      Packed    [!split] Packed [g6, !split], d_saa
+//   d_sidx, split         -                  Plain, never NT    -
+//   d_sslot (d_sidx null) Sorted32           Sorted32           Sorted32 [g6, d_saj]
+//   d_vcode [g6, !crow,   ValueCodes         ValueCodes         -
+//     !d_sslot, !split]
+//   tune.nt == 1 [!crow]  NT                 NT                 -
+//   otherwise             Plain              Plain              Plain
+//
+// "+ Wide": of a split plan the narrow / coded blocks (d_nblocks) take the
+// row's mode and the wide ones (d_wblocks) kStreamWide in a second launch; the
+// dot's partials would then come from two launches, so MultDot takes the
+// original arrays in one. Codes(NT): kStreamCodesNT when tune.nt == 1. d_sslot
+// stays allocated beside d_sidx (update_values re-orders new values by it), so
+// d_sidx is tested first.
+StreamLayout stream_layout(const aijhip_mat &A, StreamAsk ask) {
+    const Plan &P = A.plan;
+    const bool fused = ask == StreamAsk::Fused, g6 = P.tune.geom == 6, crow = A.compressed, split = P.n_wblocks > 0;
+    StreamLayout D;
+    StreamPart &M = D.main;
+    M = {P.d_blocks, P.n_blocks, kStreamPlain, A.d_aj, A.d_aa};
+    if (P.d_pid && (fused || (g6 && !crow))) {  // row patterns / templates (planned at geometry 6, full rows)
+        D.kind = !g6 ? StreamLayout::kInvalid : P.d_pval ? StreamLayout::kTemplate : StreamLayout::kPattern;
+        return D;
     }
-    // Column codes (Plan::d_code; geometry 6, full-row lists): MatMult,
-    // MatMultAdd and the CG's fused dot; with a coded / uncoded split the dot's
-    // partials would come from two launches, so that case takes aj
-    if constexpr (kGeom6) {
-        if (P.d_code && !L.ridx && (P.n_wblocks == 0 || !dpart)) {
-            const BlockDesc *cb = P.n_wblocks ? P.d_nblocks : P.d_blocks;
-            const int32_t nc = P.n_wblocks ? P.n_nblocks : P.n_blocks;
-#define AIJHIP_SC(ADD, NTM)                                                                                       \
-    if (nc > 0)                                                                                                   \
-        hipLaunchKernelGGL((k_spmv_stream<T, CAP, RPT, false, NTM, OpMult<ADD>>), dim3(nc), dim3(T), 0, s, cb, nc, \
-                           (int)P.tune.exact, L.rai, nullptr, reinterpret_cast<const int32_t *>(P.d_code), A.d_aa, \
-                           OpMult<ADD>{x, z, y, dpart != nullptr}, dpart, stop, nullptr, P.d_cmeta);     \
-    if (P.n_wblocks > 0)                                                                                          \
-        hipLaunchKernelGGL((k_spmv_stream<T, CAP, RPT, false, kWideMode, OpMult<ADD>>), dim3(P.n_wblocks), dim3(T), 0, sw, \
-                           P.d_wblocks, P.n_wblocks, (int)P.tune.exact, L.rai, nullptr, A.d_aj, A.d_aa,           \
-                           OpMult<ADD>{x, z, y, false}, nullptr, stop, nullptr, nullptr);                \
-    return
-            // branch-free phase 1 (bit 64): FEM stand-in 229.7 vs 253.5 us
-            // predicated (profiles/r04/s1/bf_fem.jsonl)
-            if (add) {
-                if (P.tune.nt == 1) { AIJHIP_SC(true, 97); }
-                AIJHIP_SC(true, 96);
-            }
-            if (P.tune.nt == 1) { AIJHIP_SC(false, 97); }
-            AIJHIP_SC(false, 96);
-#undef AIJHIP_SC
-        }
-    }
-    // Gather-ordered blocks (Plan::d_sslot): the sorted copy, every variant
-    // (MatMult / MatMultAdd, full or compressed rows, dot epilogue)
-    // (with the narrow / wide split, the dot epilogue's partials would come
-    // from two launches: the CG's fused product takes the original arrays)
-    if (P.d_sidx && (P.n_wblocks == 0 || !dpart)) {  // packed columns and slots, a word per entry
-        const BlockDesc *nb = P.n_wblocks ? P.d_nblocks : P.d_blocks;
-        const int32_t nn = P.n_wblocks ? P.n_nblocks : P.n_blocks;
-#define AIJHIP_SS(ADD, CROW, NTM)                                                                              \
-    if (nn > 0)                                                                                                \
-        hipLaunchKernelGGL((k_spmv_stream<T, CAP, RPT, CROW, NTM, OpMult<ADD>>), dim3(nn), dim3(T), 0, s, nb, nn, \
-                           (int)P.tune.exact, L.rai, L.ridx, reinterpret_cast<const int32_t *>(P.d_sidx), P.d_saa, \
-                           OpMult<ADD>{x, z, y, dpart != nullptr}, dpart, stop, nullptr, P.d_sbase);  \
-    if (P.n_wblocks > 0)                                                                                       \
-        hipLaunchKernelGGL((k_spmv_stream<T, CAP, RPT, CROW, kWideMode, OpMult<ADD>>), dim3(P.n_wblocks), dim3(T), 0, sw, \
-                           P.d_wblocks, P.n_wblocks, (int)P.tune.exact, L.rai, L.ridx, A.d_aj, A.d_aa,         \
-                           OpMult<ADD>{x, z, y, false}, nullptr, stop, nullptr, nullptr);             \
-    return
-        // value codes (bit 128: 16-bit indices into the dictionary for aa)
-        if constexpr (kGeom6) {
-            if (P.d_svcode && !L.ridx) {
-#define AIJHIP_SV(ADD)                                                                                         \
-    if (nn > 0)                                                                                                \
-        hipLaunchKernelGGL((k_spmv_stream<T, CAP, RPT, false, 208, OpMult<ADD>>), dim3(nn), dim3(T), 0, s, nb, nn, \
-                           (int)P.tune.exact, L.rai, nullptr, reinterpret_cast<const int32_t *>(P.d_sidx),      \
-                           reinterpret_cast<const double *>(P.d_svcode), OpMult<ADD>{x, z, y, dpart != nullptr}, \
-                           dpart, stop, nullptr, P.d_sbase, P.d_vdict, P.n_vdict);                             \
-    if (P.n_wblocks > 0)                                                                                       \
-        hipLaunchKernelGGL((k_spmv_stream<T, CAP, RPT, false, kWideMode, OpMult<ADD>>), dim3(P.n_wblocks), dim3(T), 0, \
-                           sw, P.d_wblocks, P.n_wblocks, (int)P.tune.exact, L.rai, nullptr, A.d_aj, A.d_aa,     \
-                           OpMult<ADD>{x, z, y, false}, nullptr, stop, nullptr, nullptr);                      \
-    return
-                if (add) { AIJHIP_SV(true); }
-                AIJHIP_SV(false);
-#undef AIJHIP_SV
-            }
-        }
-        // branch-free phase 1 (bit 64): skewed stand-in 331.9 vs 340.2 us
-        // predicated (profiles/r04/s1/bf_skewed.jsonl)
-        if (add && L.ridx) { AIJHIP_SS(true, true, 80); }
-        if (add) { AIJHIP_SS(true, false, 80); }
-        if (L.ridx) { AIJHIP_SS(false, true, 80); }
-        AIJHIP_SS(false, false, 80);
-#undef AIJHIP_SS
-    }
-    if (P.d_sidx) {  // split plan, fused dot: the original arrays in one launch
-        if (L.ridx) { AIJHIP_SL(false, true, 0); }
-        AIJHIP_SL(false, false, 0);
-    }
-    if (P.d_sslot) {
-#define AIJHIP_SS(ADD, CROW)                                                                                \
-    hipLaunchKernelGGL((k_spmv_stream<T, CAP, RPT, CROW, 8, OpMult<ADD>>), dim3(P.n_blocks), dim3(T), 0, s, \
-                       P.d_blocks, P.n_blocks, (int)P.tune.exact, L.rai, L.ridx, P.d_saj, P.d_saa,          \
-                       OpMult<ADD>{x, z, y, dpart != nullptr}, dpart, stop, P.d_sslot, nullptr);   \
-    return
-        if (add && L.ridx) { AIJHIP_SS(true, true); }
-        if (add) { AIJHIP_SS(true, false); }
-        if (L.ridx) { AIJHIP_SS(false, true); }
-        AIJHIP_SS(false, false);
-#undef AIJHIP_SS
-    }
+    // may this caller take the coded / packed arrays? then, of a split plan, for the narrow blocks
+    const bool alt = fused ? g6 && !split : !split || ask == StreamAsk::Mult;
+    const BlockDesc *nb = split ? P.d_nblocks : P.d_blocks;
+    const int32_t nn = split ? P.n_nblocks : P.n_blocks;
+    const auto *code = reinterpret_cast<const int32_t *>(P.d_code), *sidx = reinterpret_cast<const int32_t *>(P.d_sidx);
+    // (branch-free phase 1 for the coded and the packed blocks: FEM stand-in
+    // 229.7 vs 253.5 us predicated, skewed stand-in 331.9 vs 340.2 us,
+    // profiles/r04/s1/bf_fem.jsonl, bf_skewed.jsonl. Gather-ordered blocks:
+    // the products land in their storage slots, so the dot and the fused
+    // epilogues see the same sums as from aj / aa)
+    if (P.d_code && alt && g6 && !crow)
+        M = {nb, nn, !fused && P.tune.nt == 1 ? kStreamCodesNT : kStreamCodes, code, A.d_aa, nullptr, P.d_cmeta};
+    else if (P.d_sidx && alt && !fused && g6 && P.d_svcode && !crow)
+        M = {nb, nn, kStreamPackedValueCodes, sidx, reinterpret_cast<const double *>(P.d_svcode), nullptr, P.d_sbase,
+             P.d_vdict, P.n_vdict};
+    else if (P.d_sidx && alt)
+        M = {nb, nn, kStreamPacked, sidx, P.d_saa, nullptr, P.d_sbase};
+    else if (P.d_sidx && !fused)
+        ;  // split plan, fused dot: the original arrays in one launch
+    else if (P.d_sslot && (!fused || (P.d_saj && g6)))
+        M = {P.d_blocks, P.n_blocks, kStreamSorted32, P.d_saj, P.d_saa, P.d_sslot};
+    else if (!fused && g6 && P.d_vcode && !P.d_sslot && !crow && !split)  // the predicated phase 1
+        M = {P.d_blocks, P.n_blocks, kStreamValueCodes, A.d_aj, reinterpret_cast<const double *>(P.d_vcode), nullptr,
+             nullptr, P.d_vdict, P.n_vdict};
+    else if (!fused && P.tune.nt == 1 && !crow)  // (compressed rows, MPIAIJ's off-diagonal blocks, keep plain loads)
+        M.mode = kStreamNT;
     // (the plain aj blocks keep the predicated phase 1: branch-free measured
     // 505.9 vs 492.8 us at 300^3, profiles/r04/s1/bf_poisson.jsonl — for the
     // 7-point rows the clamped lanes' extra loads and gathers cost more than
@@ -2121,36 +2062,104 @@ static void stream_dispatch(const aijhip_mat &A, const Plan &P, const RowList &L
     // at 87 VGPRs it holds 4-5 waves per SIMD against 8, and the hardware's
     // four resident workgroups per CU overlap each other's phases better,
     // profiles/r05/l/ab_pipe.jsonl; withdrawn, option 16 reserved)
-    // value codes on the plain blocks: the predicated phase 1 with 16-bit
-    // indices into the dictionary for aa (bit 128)
-    if constexpr (kGeom6) {
-        if (P.d_vcode && !P.d_sslot && !L.ridx && P.n_wblocks == 0) {
-#define AIJHIP_PV(ADD)                                                                                     \
-    hipLaunchKernelGGL((k_spmv_stream<T, CAP, RPT, false, 128, OpMult<ADD>>), dim3(P.n_blocks), dim3(T), 0, s, \
-                       P.d_blocks, P.n_blocks, (int)P.tune.exact, L.rai, nullptr, A.d_aj,                  \
-                       reinterpret_cast<const double *>(P.d_vcode), OpMult<ADD>{x, z, y, dpart != nullptr}, \
-                       dpart, stop, nullptr, nullptr, P.d_vdict, P.n_vdict);                               \
-    return
-            if (add) { AIJHIP_PV(true); }
-            AIJHIP_PV(false);
-#undef AIJHIP_PV
-        }
-    }
-    // non-temporal matrix loads: the plain full-row MatMult / MatMultAdd
-    // (the compressed-row form, MPIAIJ's off-diagonal blocks, keeps plain loads)
-    if (P.tune.nt == 1 && !L.ridx) {
-        if (add) { AIJHIP_SL(true, false, 1); }
-        AIJHIP_SL(false, false, 1);
-    }
-    if (add && L.ridx) { AIJHIP_SL(true, true, 0); }
-    if (add) { AIJHIP_SL(true, false, 0); }
-    if (L.ridx) { AIJHIP_SL(false, true, 0); }
-    AIJHIP_SL(false, false, 0);
-#undef AIJHIP_SL
+    // The wide blocks (few long rows of scattered columns each, split from the
+    // narrow ones) on the branch-free phase 1 with non-temporal matrix loads:
+    // with the predicated form each lane's eight scattered gathers waited on one
+    // another (vmcnt(0) per pair), and a launch of a few dozen such blocks is
+    // one block's latency — 29 us of the skewed stand-in's serial 331 us
+    // (round 5, profiles/r05/x)
+    if (split && (M.mode & (kModeCodes | kModePacked)))
+        D.wide = {P.d_wblocks, P.n_wblocks, kStreamWide, A.d_aj, A.d_aa};
+    return D;
 }
 
-#define AIJHIP_GEOM(G) kStreamGeoms[G].threads, kStreamGeoms[G].nnz_cap, \
-                       kStreamGeoms[G].rows / kStreamGeoms[G].threads
+// The k_spmv_stream instantiations each class of caller may reach (no other
+// is compiled): MatMult / MatMultAdd, and the fused ops.
+struct MultVariants {
+    static constexpr bool has(int geom, int mode, bool crow) {
+        const bool any = mode == kStreamPlain || mode == kStreamSorted32 || mode == kStreamWide || mode == kStreamPacked;
+        return any || (!crow && (mode == kStreamNT || geom == 6));
+    }
+};
+struct FusedVariants {
+    static constexpr bool has(int geom, int mode, bool crow) {
+        const bool alt = mode == kStreamSorted32 || mode == kStreamPacked || mode == kStreamCodes;
+        return !crow && (mode == kStreamPlain || (geom == 6 && alt));
+    }
+};
+
+// The runtime (geometry, mode, crow) as template arguments: f(G, MODE, CROW) with
+// std::integral_constants for the combinations Variants has, false for any other.
+template <class Variants, int G, int MODE, bool CROW, class F>
+static bool stream_variant_is(int mode, bool crow, F &f) {
+    if constexpr (Variants::has(G, MODE, CROW)) {
+        if (mode == MODE && crow == CROW) {
+            f(std::integral_constant<int, G>{}, std::integral_constant<int, MODE>{}, std::bool_constant<CROW>{});
+            return true;
+        }
+    }
+    return false;
+}
+template <class Variants, int G, class F, size_t... I>
+static bool stream_variant_at(int mode, bool crow, F &f, std::index_sequence<I...>) {
+    return (stream_variant_is<Variants, G, kStreamModes[I / 2], I % 2 != 0>(mode, crow, f) || ...);
+}
+// Every geometry is dispatched explicitly: the kernel's LDS size must be the
+// one the plan's row blocks were cut for.
+template <class Variants, class F>
+static bool stream_variant(int geom, int mode, bool crow, F f) {
+    static_assert(kNumStreamGeoms == 10, "update the geometry dispatch");
+    constexpr std::make_index_sequence<2 * kNumStreamModes> V{};
+    switch (geom) {
+        case 0: return stream_variant_at<Variants, 0>(mode, crow, f, V);
+        case 1: return stream_variant_at<Variants, 1>(mode, crow, f, V);
+        case 2: return stream_variant_at<Variants, 2>(mode, crow, f, V);
+        case 3: return stream_variant_at<Variants, 3>(mode, crow, f, V);
+        case 4: return stream_variant_at<Variants, 4>(mode, crow, f, V);
+        case 5: return stream_variant_at<Variants, 5>(mode, crow, f, V);
+        case 6: return stream_variant_at<Variants, 6>(mode, crow, f, V);
+        case 7: return stream_variant_at<Variants, 7>(mode, crow, f, V);
+        case 8: return stream_variant_at<Variants, 8>(mode, crow, f, V);
+        case 9: return stream_variant_at<Variants, 9>(mode, crow, f, V);
+        default: return false;
+    }
+}
+
+// The one k_spmv_stream launch: a part's blocks at the plan's geometry.
+template <class Variants, class Op>
+static hipError_t launch_stream_part(const aijhip_mat &A, const StreamPart &p, int exact, const Op &op, double *dpart,
+                                     const int *stop, hipStream_t s) {
+    if (p.n_blocks <= 0) return hipSuccess;
+    const RowList L = row_list(A);
+    const bool ok = stream_variant<Variants>(A.plan.tune.geom, p.mode, L.ridx != nullptr, [&](auto G, auto M, auto C) {
+        constexpr StreamGeom g = kStreamGeoms[decltype(G)::value];
+        hipLaunchKernelGGL((k_spmv_stream<g.threads, g.nnz_cap, g.rows / g.threads, decltype(C)::value,
+                                          decltype(M)::value, Op>),
+                           dim3(p.n_blocks), dim3(g.threads), 0, s, p.blocks, p.n_blocks, exact, L.rai, L.ridx, p.aj,
+                           p.aa, op, dpart, stop, p.sslot, p.aux, p.vdict, p.n_vdict);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+// A layout's template, pattern or main STREAM launch (the wide part is launch_stream's).
+template <class Variants, class Op>
+static hipError_t launch_layout(const aijhip_mat &A, const StreamLayout &D, int exact, const Op &op, double *dpart,
+                                const int *stop, hipStream_t s) {
+    const Plan &P = A.plan;
+    constexpr StreamGeom g6 = kStreamGeoms[6];
+    switch (D.kind) {
+        case StreamLayout::kTemplate: {
+            const hipError_t e = launch_template(A, op, dpart, s, stop);
+            return e != hipSuccess ? e : hipGetLastError();
+        }
+        case StreamLayout::kPattern:
+            hipLaunchKernelGGL((k_spmv_pattern<g6.threads, g6.nnz_cap, Op>), dim3(P.n_blocks), dim3(g6.threads), 0, s,
+                               P.d_blocks, A.d_ai, P.d_pid, P.d_ptab, P.n_ptab, P.n_pat, A.d_aa, op, dpart, stop);
+            return hipGetLastError();
+        case StreamLayout::kStream: return launch_stream_part<Variants>(A, D.main, exact, op, dpart, stop, s);
+        default: return hipErrorInvalidValue;
+    }
+}
 
 bool stream_dot_fusable(const aijhip_mat &A) {
     const Plan &P = A.plan;
@@ -2171,55 +2180,8 @@ static hipError_t launch_stream_op(const aijhip_mat &A, const Op &op, double *dp
     if (!stream_mg_fusable(A)) return hipErrorInvalidValue;
     const Plan &P = A.plan;
     if (P.n_blocks == 0) return hipSuccess;
-    const int ex = exact < 0 ? (int)P.tune.exact : exact;
-    if (P.d_pid && P.d_pval) {  // row templates (planned at geometry 6)
-        if (P.tune.geom != 6) return hipErrorInvalidValue;
-        const hipError_t e = launch_template(A, op, dpart, s, stop);
-        return e != hipSuccess ? e : hipGetLastError();
-    }
-    if (P.d_pid) {  // row patterns (planned at geometry 6)
-        if (P.tune.geom != 6) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_spmv_pattern<kStreamGeoms[6].threads, kStreamGeoms[6].nnz_cap, Op>), dim3(P.n_blocks),
-                           dim3(kStreamGeoms[6].threads), 0, s, P.d_blocks, A.d_ai, P.d_pid, P.d_ptab, P.n_ptab,
-                           P.n_pat, A.d_aa, op, dpart, stop);
-        return hipGetLastError();
-    }
-    if (P.d_code && P.n_wblocks == 0 && P.tune.geom == 6) {  // column codes (the planner builds them at geometry 6)
-        hipLaunchKernelGGL((k_spmv_stream<AIJHIP_GEOM(6), false, 96, Op>), dim3(P.n_blocks),
-                           dim3(kStreamGeoms[6].threads), 0, s, P.d_blocks, P.n_blocks, ex, A.d_ai, nullptr,
-                           reinterpret_cast<const int32_t *>(P.d_code), A.d_aa, op, dpart, stop, nullptr,
-                           P.d_cmeta);
-        return hipGetLastError();
-    }
-    // gather-ordered blocks: the products land in their storage slots, so the
-    // fused epilogues see the same sums as from aj / aa
-    if (P.d_sidx && P.n_wblocks == 0 && P.tune.geom == 6) {  // packed columns (planned at geometry 6)
-        hipLaunchKernelGGL((k_spmv_stream<AIJHIP_GEOM(6), false, 80, Op>), dim3(P.n_blocks),
-                           dim3(kStreamGeoms[6].threads), 0, s, P.d_blocks, P.n_blocks, ex, A.d_ai, nullptr,
-                           reinterpret_cast<const int32_t *>(P.d_sidx), P.d_saa, op, dpart, stop, nullptr,
-                           P.d_sbase);
-        return hipGetLastError();
-    }
-    if (P.d_sslot && P.d_saj && P.tune.geom == 6) {  // 32-bit sorted columns
-        hipLaunchKernelGGL((k_spmv_stream<AIJHIP_GEOM(6), false, 8, Op>), dim3(P.n_blocks),
-                           dim3(kStreamGeoms[6].threads), 0, s, P.d_blocks, P.n_blocks, ex, A.d_ai, nullptr,
-                           P.d_saj, P.d_saa, op, dpart, stop, P.d_sslot, nullptr);
-        return hipGetLastError();
-    }
-    static_assert(kNumStreamGeoms == 10, "update the geometry dispatch");
-#define AIJHIP_OG(G)                                                                                          \
-    case G:                                                                                                      \
-        hipLaunchKernelGGL((k_spmv_stream<AIJHIP_GEOM(G), false, 0, Op>), dim3(P.n_blocks),                      \
-                           dim3(kStreamGeoms[G].threads), 0, s, P.d_blocks, P.n_blocks, ex, A.d_ai, nullptr, A.d_aj, \
-                           A.d_aa, op, dpart, stop, nullptr, nullptr);                                  \
-        break
-    switch (P.tune.geom) {
-        AIJHIP_OG(0); AIJHIP_OG(1); AIJHIP_OG(2); AIJHIP_OG(3); AIJHIP_OG(4);
-        AIJHIP_OG(5); AIJHIP_OG(6); AIJHIP_OG(7); AIJHIP_OG(8); AIJHIP_OG(9);
-        default: return hipErrorInvalidValue;
-    }
-#undef AIJHIP_OG
-    return hipGetLastError();
+    return launch_layout<FusedVariants>(A, stream_layout(A, StreamAsk::Fused), exact < 0 ? (int)P.tune.exact : exact,
+                                        op, dpart, stop, s);
 }
 
 hipError_t launch_stream_blocks(const aijhip_mat &A, int32_t b0, int32_t nb, const double *x, double *y,
@@ -2227,32 +2189,18 @@ hipError_t launch_stream_blocks(const aijhip_mat &A, int32_t b0, int32_t nb, con
     const Plan &P = A.plan;
     if (P.kernel != AIJHIP_KERNEL_STREAM || A.compressed || P.n_longs > 0 || b0 < 0 || b0 + nb > P.n_blocks)
         return hipErrorInvalidValue;
-    if (nb <= 0) return hipSuccess;
-    static_assert(kNumStreamGeoms == 10, "update the geometry dispatch");
-#define AIJHIP_BG(G)                                                                                             \
-    case G:                                                                                                      \
-        hipLaunchKernelGGL((k_spmv_stream<AIJHIP_GEOM(G), false, 0, OpMult<false>>), dim3(nb),                   \
-                           dim3(kStreamGeoms[G].threads), 0, s, P.d_blocks + b0, nb, (int)P.tune.exact, A.d_ai,  \
-                           nullptr, A.d_aj, A.d_aa, OpMult<false>{x, nullptr, y, false}, nullptr, nullptr,      \
-                           nullptr, nullptr);                                                                    \
-        break
-    switch (P.tune.geom) {
-        AIJHIP_BG(0); AIJHIP_BG(1); AIJHIP_BG(2); AIJHIP_BG(3); AIJHIP_BG(4);
-        AIJHIP_BG(5); AIJHIP_BG(6); AIJHIP_BG(7); AIJHIP_BG(8); AIJHIP_BG(9);
-        default: return hipErrorInvalidValue;
-    }
-#undef AIJHIP_BG
-    return hipGetLastError();
+    const StreamPart part = {P.d_blocks + b0, nb, kStreamPlain, A.d_aj, A.d_aa};
+    return launch_stream_part<MultVariants>(A, part, (int)P.tune.exact, OpMult<false>{x, nullptr, y, false}, nullptr,
+                                            nullptr, s);
 }
 
 hipError_t launch_mg_resid(const aijhip_mat &A, const double *x, const double *b, double *r, hipStream_t s,
-                           bool nt, const int *stop) {
-    if (nt) return launch_stream_op(A, OpMgResid<true>{x, b, r}, nullptr, s, -1, stop);
-    return launch_stream_op(A, OpMgResid<false>{x, b, r}, nullptr, s, -1, stop);
+                           const int *stop) {
+    return launch_stream_op(A, OpMgResid<true>{x, b, r}, nullptr, s, -1, stop);
 }
 
 hipError_t launch_mg_post(const aijhip_mat &A, const double *t, const double *b, const double *dinv, double *x,
-                          double *dpart, hipStream_t s, bool nt, const int *stop, const double *tdinv) {
+                          double *dpart, hipStream_t s, const int *stop, const double *tdinv) {
     if (tdinv && A.plan.d_pid && A.plan.d_pval) {  // row templates: D^-1 per template
         if (A.plan.tmpl_diag && template_pipelined(A.plan))  // the pipelined launch: t[r] from the diagonal slot
             return launch_stream_op(A, OpMgPost<true, true, true>{t, b, dinv, x, dpart != nullptr, A.plan.d_pid, tdinv},
@@ -2260,8 +2208,7 @@ hipError_t launch_mg_post(const aijhip_mat &A, const double *t, const double *b,
         return launch_stream_op(A, OpMgPost<true, true>{t, b, dinv, x, dpart != nullptr, A.plan.d_pid, tdinv}, dpart,
                                 s, -1, stop);
     }
-    if (nt) return launch_stream_op(A, OpMgPost<true>{t, b, dinv, x, dpart != nullptr}, dpart, s, -1, stop);
-    return launch_stream_op(A, OpMgPost<false>{t, b, dinv, x, dpart != nullptr}, dpart, s, -1, stop);
+    return launch_stream_op(A, OpMgPost<true>{t, b, dinv, x, dpart != nullptr}, dpart, s, -1, stop);
 }
 
 hipError_t launch_dinv_mult(const aijhip_mat &A, const double *dinv, const double *x, double *y, hipStream_t s) {
@@ -2303,18 +2250,17 @@ hipError_t launch_stream(const aijhip_mat &A, const double *x, const double *z, 
                                 P.d_partials, z, y);
         e = hipGetLastError();
     }
-    // Every geometry is dispatched explicitly: the kernel's LDS size must be
-    // the one the plan's row blocks were cut for.
-    static_assert(kNumStreamGeoms == 10, "update the geometry dispatch");
+    // the row blocks on s, and the wide ones of a split plan on sw
     if (e == hipSuccess && P.n_blocks > 0) {
-#define AIJHIP_SG(G) case G: stream_dispatch<AIJHIP_GEOM(G)>(A, P, L, x, z, y, add, s, dpart, stop, sw); break
-        switch (P.tune.geom) {
-            AIJHIP_SG(0); AIJHIP_SG(1); AIJHIP_SG(2); AIJHIP_SG(3); AIJHIP_SG(4);
-            AIJHIP_SG(5); AIJHIP_SG(6); AIJHIP_SG(7); AIJHIP_SG(8); AIJHIP_SG(9);
-            default: e = hipErrorInvalidValue; break;
-        }
-#undef AIJHIP_SG
-        if (e == hipSuccess) e = hipGetLastError();
+        const StreamLayout D = stream_layout(A, dpart ? StreamAsk::MultDot : StreamAsk::Mult);
+        auto run = [&](auto ADD) {
+            using Op = OpMult<decltype(ADD)::value>;
+            const int ex = (int)P.tune.exact;
+            const hipError_t r = launch_layout<MultVariants>(A, D, ex, Op{x, z, y, dpart != nullptr}, dpart, stop, s);
+            if (r != hipSuccess) return r;
+            return launch_stream_part<MultVariants>(A, D.wide, ex, Op{x, z, y, false}, nullptr, stop, sw);
+        };
+        e = add ? run(std::true_type{}) : run(std::false_type{});
     }
     // the join is recorded even after a failed launch, so the caller's stream
     // never runs ahead of side-stream work that was already queued

@@ -2197,7 +2197,7 @@ int vcycle(Hierarchy &H, const double *b0, double *x0, hipStream_t s, const int 
         if (fused(L)) {
             const bool ex = exchanges(L.op);
             if (ex && (rc = aijhip_mpi::halo_post(L.op, X(l), s))) return rc;
-            if ((e = aijhip::launch_mg_resid(*L.Ad, X(l), B(l), L.r, s, true, stop)) != hipSuccess)
+            if ((e = aijhip::launch_mg_resid(*L.Ad, X(l), B(l), L.r, s, stop)) != hipSuccess)
                 return ex ? aijhip_mpi::halo_abort(L.op, s, gerr(e, "residual")) : gerr(e, "residual");
             if (ex && (rc = aijhip_mpi::halo_finish(L.op, s))) return rc;
             if ((rc = offdiag_axpy(L, nullptr, L.r, s, stop))) return rc;
@@ -2216,7 +2216,7 @@ int vcycle(Hierarchy &H, const double *b0, double *x0, hipStream_t s, const int 
             if ((rc = transfer(H.lv[l + 1].op, L.Pd, L.Po, X(l + 1), X(l), L.r, true, s, stop))) return rc;
             const bool ex = exchanges(L.op);
             if (ex && (rc = aijhip_mpi::halo_post(L.op, L.r, s))) return rc;
-            if ((e = aijhip::launch_mg_post(*L.Ad, L.r, B(l), L.dinv, X(l), nullptr, s, true, stop)) != hipSuccess)
+            if ((e = aijhip::launch_mg_post(*L.Ad, L.r, B(l), L.dinv, X(l), nullptr, s, stop)) != hipSuccess)
                 return ex ? aijhip_mpi::halo_abort(L.op, s, gerr(e, "post-smoothing")) : gerr(e, "post-smoothing");
             if (ex && (rc = aijhip_mpi::halo_finish(L.op, s))) return rc;
             if ((rc = offdiag_axpy(L, L.dinv, X(l), s, stop))) return rc;

@@ -370,7 +370,7 @@ hipError_t vcycle(aijhip_ksp *K, const double *b0, double *x0, hipStream_t s, do
                 hipLaunchKernelGGL(k_jacobi_t, g, t, 0, s, (int64_t)L.m, L.A->plan.d_pid, L.tdinv, B(l), X(l), stop);
             else
                 hipLaunchKernelGGL(k_jacobi, g, t, 0, s, (int64_t)L.m, L.dinv, B(l), X(l), stop);
-            if ((e = aijhip::launch_mg_resid(*L.A, X(l), B(l), L.r, s, true, stop)) != hipSuccess) return e;
+            if ((e = aijhip::launch_mg_resid(*L.A, X(l), B(l), L.r, s, stop)) != hipSuccess) return e;
         } else {
             hipLaunchKernelGGL(k_jacobi, g, t, 0, s, (int64_t)L.m, L.dinv, B(l), X(l), stop);  // smoothd
             if ((e = aijhip::launch_mult(*L.A, X(l), nullptr, L.r, false, s, stop)) != hipSuccess) return e;
@@ -386,7 +386,7 @@ hipError_t vcycle(aijhip_ksp *K, const double *b0, double *x0, hipStream_t s, do
             // MatInterpolateAdd into the scratch: t = x + P x_c, then smoothu
             if ((e = aijhip::launch_mult(*L.P, X(l + 1), X(l), L.r, true, s, stop)) != hipSuccess) return e;
             double *dp = (l == 0 && dots) ? dots : nullptr;
-            if ((e = aijhip::launch_mg_post(*L.A, L.r, B(l), L.dinv, X(l), dp, s, true, stop, L.tdinv)) != hipSuccess)
+            if ((e = aijhip::launch_mg_post(*L.A, L.r, B(l), L.dinv, X(l), dp, s, stop, L.tdinv)) != hipSuccess)
                 return e;
             if (dp && dots_done) *dots_done = true;
         } else {
