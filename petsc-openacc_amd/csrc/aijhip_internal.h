@@ -426,10 +426,11 @@ void host_pipe_free(HostPipe *p);
 
 // The V-cycle of a set-up GAMG KSP (ksp.hip) as a preconditioner of another
 // solver (the distributed CG's block-Jacobi sub-PC, ksp_mpi.hip): x = B b on
-// `s`. When the finest post-smoothing carried the z.z / z.b partials, *dots
-// points at them (2 x *nbz doubles), else NULL.
-hipError_t ksp_pc_vcycle(aijhip_ksp *K, const double *b, double *x, hipStream_t s, const double **dots,
-                         int *nbz, const int *stop = nullptr);
+// `s` (mg_cycle.h's walker over K's levels). dots != NULL: when the finest
+// post-smoothing carried the z.z / z.b partials, *dots points at them
+// (2 x *nbz doubles), else it is NULL. Returns an AIJHIP_* code.
+int ksp_pc_vcycle(aijhip_ksp *K, const double *b, double *x, hipStream_t s, const int *stop, const double **dots,
+                  int *nbz);
 
 // A fresh value for aijhip_mat::plan_gen.
 uint64_t next_plan_gen();

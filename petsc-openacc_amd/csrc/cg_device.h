@@ -1,6 +1,7 @@
-// cg_device.h — KSPSolve_CG's device-side scalar state and reductions,
-// shared by the single-GPU solver (ksp.hip) and the row-partitioned one
-// (ksp_mpi.hip). Not part of the ABI.
+// cg_device.h — KSPSolve_CG's device-side scalar state, reductions and vector
+// kernels, launched by the one CG driver (cg_solve.hip) for the single-GPU
+// handle (ksp.hip) and the row-partitioned one (ksp_mpi.hip). Not part of the
+// ABI.
 //
 // The scalar steps restate PETSc 3.7.6 KSPSolve_CG [ext]
 // (src/ksp/ksp/impls/cg/cg.c) and KSPConvergedDefault [ext]: each takes the
@@ -334,6 +335,64 @@ __global__ __launch_bounds__(kVecThreads) void k_update(int64_t n, double *r, do
         v = bsum<kVecThreads>(zr, scratch); if (threadIdx.x == 0) part[1 * nb + blockIdx.x] = v;
     }
     v = bsum<kVecThreads>(rr, scratch); if (threadIdx.x == 0) part[2 * nb + blockIdx.x] = v;
+}
+
+// K3 / K5 / init: this device's partial lists summed in the fixed
+// reduce_parts order, then either the scalar step in place (red == NULL: one
+// rank) or the sums into red[] for the all-reduce, which k_step_* follows.
+__global__ __launch_bounds__(kRedThreads) void k_sum_init(const double *part, int nb, double *red, CGState *S,
+                                                          double *hist, CGParams p) {
+    __shared__ double scratch[kRedThreads / 64];
+    const double zz = reduce_parts(part + 0 * nb, nb, scratch);
+    const double zr = reduce_parts(part + 1 * nb, nb, scratch);
+    const double rr = reduce_parts(part + 2 * nb, nb, scratch);
+    const double ss = reduce_parts(part + 3 * nb, nb, scratch);
+    if (threadIdx.x != 0) return;
+    if (!red) step_init(zz, zr, rr, ss, S, hist, p);
+    else { red[0] = zz; red[1] = zr; red[2] = rr; red[3] = ss; }
+}
+
+// dpi: the A_d list (the SpMV epilogue's or k_dot's partials), then the A_o
+// corrections (opart[0, nob), ksp_mpi.hip k_offdiag) when there are any.
+__global__ __launch_bounds__(kRedThreads) void k_sum_dpi(const double *part, int nb, const double *opart, int nob,
+                                                         double *red, CGState *S) {
+    __shared__ double scratch[kRedThreads / 64];
+    if (S->done) return;
+    double v = reduce_parts(part, nb, scratch);
+    if (nob > 0) {
+        const double o = reduce_parts(opart, nob, scratch);
+        v += o;
+    }
+    if (threadIdx.x != 0) return;
+    if (!red) step_dpi(v, S);
+    else red[0] = v;
+}
+
+// zz, zr come from pz[0, nbz) and pz[nbz, 2 nbz) (the vector kernels' slots 0
+// and 1, or the fused V-cycle's finest post-smoothing); rr from pr[0, nbr).
+__global__ __launch_bounds__(kRedThreads) void k_sum_iter(const double *pz, int nbz, const double *pr, int nbr,
+                                                          double *red, CGState *S, double *hist, CGParams p) {
+    __shared__ double scratch[kRedThreads / 64];
+    if (S->done) return;
+    const double zz = reduce_parts(pz, nbz, scratch);
+    const double zr = reduce_parts(pz + nbz, nbz, scratch);
+    const double rr = reduce_parts(pr, nbr, scratch);
+    if (threadIdx.x != 0) return;
+    if (!red) step_iter(zz, zr, rr, S, hist, p);
+    else { red[0] = zz; red[1] = zr; red[2] = rr; }
+}
+
+// The scalar steps on all-reduced sums (more than one rank).
+__global__ void k_step_init(const double *red, CGState *S, double *hist, CGParams p) {
+    if (threadIdx.x == 0) step_init(red[0], red[1], red[2], red[3], S, hist, p);
+}
+
+__global__ void k_step_dpi(const double *red, CGState *S) {
+    if (threadIdx.x == 0 && !S->done) step_dpi(red[0], S);
+}
+
+__global__ void k_step_iter(const double *red, CGState *S, double *hist, CGParams p) {
+    if (threadIdx.x == 0 && !S->done) step_iter(red[0], red[1], red[2], S, hist, p);
 }
 
 }  // namespace

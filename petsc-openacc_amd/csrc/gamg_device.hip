@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "dscan.h"
+#include "emax_device.h"
 #include "gamg_device.h"
 
 namespace {
@@ -417,20 +418,6 @@ __global__ void k_count_value(int32_t m, const int32_t *__restrict__ x, int32_t 
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(count, (unsigned long long)__popcll(b));
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-// the power iteration's start (gamg_setup.cpp estimate_emax)
-__global__ void k_power_start(int32_t m, double *v) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    v[i] = 2.0 * ((double)(mix64(0x5EEDULL + (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ULL) >> 11) *
-                  (1.0 / 9007199254740992.0)) - 1.0;
-}
-
 constexpr int64_t kDotBlock = 256;  // gamg_setup.cpp kDotBlock
 
 // One wavefront per 256-entry block: the lanes load the block coalesced (4
@@ -471,37 +458,6 @@ __global__ __launch_bounds__(256) void k_block_dot_wave(int64_t n, const double 
         for (; k < len; ++k) s += prod[w][k];
         part[q] = s;
     }
-}
-
-// CG's emax estimate (gamg_setup.cpp estimate_emax_cg): the start, r -= a w
-// with z = D^-1 r, and p = z + b p
-__global__ void k_cgest_start(int32_t m, const double *__restrict__ dinv, double *r, double *z, double *p) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const double v = 2.0 * ((double)(mix64(0x5EEDULL + (uint64_t)(i + 1) * 0x9E3779B97F4A7C15ULL) >> 11) *
-                            (1.0 / 9007199254740992.0)) - 1.0;
-    r[i] = v;
-    z[i] = dinv[i] * v;
-    p[i] = z[i];
-}
-
-__global__ void k_cgest_update(int32_t m, double a, const double *__restrict__ w, const double *__restrict__ dinv,
-                               double *r, double *z) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const double ri = r[i] - a * w[i];
-    r[i] = ri;
-    z[i] = dinv[i] * ri;
-}
-
-__global__ void k_cgest_dir(int32_t m, double b, const double *__restrict__ z, double *p) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) p[i] = z[i] + b * p[i];
-}
-
-__global__ void k_div(int32_t m, const double *w, double nw, double *v) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) v[i] = w[i] / nw;
 }
 
 // head[i][t] = row i's t-th column of S, or i past its end (the host phase-1
@@ -1492,7 +1448,7 @@ struct EmaxJob {
                 }
                 if (m == 0) return;
                 double *p = v;
-                hipLaunchKernelGGL(k_cgest_start, dim3(g256), dim3(256), 0, js, m, dinv, r, z, p);
+                hipLaunchKernelGGL(k_cgest_start, dim3(g256), dim3(256), 0, js, m, (int64_t)0, dinv, r, z, p);
                 double rz = host_blocked_dot(z, r, m, part, h_part, &e, js);
                 if (e != hipSuccess) return;
                 for (int it = 0; it < its; ++it) {
@@ -1539,7 +1495,7 @@ struct EmaxJob {
                 h_part.cap = nb;
             }
             mark("alloc");
-            hipLaunchKernelGGL(k_power_start, dim3(g256), dim3(256), 0, js, m, v);
+            hipLaunchKernelGGL(k_power_start, dim3(g256), dim3(256), 0, js, m, (int64_t)0, v);
             const double nv = host_blocked_norm(v, m, part, h_part, &e, js);
             if (e != hipSuccess) return;
             mark("start");

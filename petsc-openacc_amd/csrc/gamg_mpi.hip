@@ -35,7 +35,8 @@
 //                owners through level l+1's plan run backwards).
 // Bulk work (the large products, the transposes, the V-cycle) is on the
 // device; the host handles boundary-sized data (ghost rows, contributions).
-// The V-cycle is PETSc's multiplicative PCMG with the reference's options
+// The V-cycle is mg_cycle.hip's walker over the per-level view that build()
+// fills: PETSc's multiplicative PCMG with the reference's options
 // (Richardson(1)+Jacobi down and up, P^T restriction, coarse Jacobi), every
 // SpMV a MatMult_MPIAIJ-shaped product with its halo on the operator's
 // exchange stream.
@@ -54,6 +55,7 @@
 #include <vector>
 
 #include "dscan.h"
+#include "emax_device.h"
 #include "gamg_device.h"
 #include "gamg_internal.h"
 #include "gamg_mpi.h"
@@ -69,20 +71,6 @@ using aijhip_mpi::mhip;
 inline unsigned nblk(int64_t n, int t = 256) { return (unsigned)std::max<int64_t>(1, (n + t - 1) / t); }
 
 // ---------------------------------------------------------------- kernels
-__device__ __forceinline__ uint64_t mix64d(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-// the single-GPU power iteration's start vector at global indices off + i
-__global__ void k_power_start_off(int32_t m, int64_t off, double *v) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    v[i] = 2.0 * ((double)(mix64d(0x5EEDULL + (uint64_t)(off + i + 1) * 0x9E3779B97F4A7C15ULL) >> 11) *
-                  (1.0 / 9007199254740992.0)) - 1.0;
-}
-
 constexpr int64_t kDotBlock = 256;
 
 __global__ void k_sumsq_blocks(int64_t n, const double *__restrict__ a, double *part) {
@@ -105,42 +93,9 @@ __global__ void k_dot_blocks(int64_t n, const double *__restrict__ a, const doub
     part[q] = s;
 }
 
-// CG's emax estimate (gamg_setup.cpp estimate_emax_cg) on the distributed
-// operator: the start b at global indices (the power iteration's), r = b,
-// z = D^-1 r, p = z; r -= a w, z = D^-1 r; p = z + b p
-__global__ void k_cgest_start_off(int32_t m, int64_t off, const double *__restrict__ dinv, double *r, double *z,
-                                  double *p) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const double v = 2.0 * ((double)(mix64d(0x5EEDULL + (uint64_t)(off + i + 1) * 0x9E3779B97F4A7C15ULL) >> 11) *
-                            (1.0 / 9007199254740992.0)) - 1.0;
-    r[i] = v;
-    z[i] = dinv[i] * v;
-    p[i] = z[i];
-}
-
-__global__ void k_cgest_update(int32_t m, double a, const double *__restrict__ w, const double *__restrict__ dinv,
-                               double *r, double *z) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const double ri = r[i] - a * w[i];
-    r[i] = ri;
-    z[i] = dinv[i] * ri;
-}
-
-__global__ void k_cgest_dir(int32_t m, double b, const double *__restrict__ z, double *p) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) p[i] = z[i] + b * p[i];
-}
-
 __global__ void k_scale_by(int32_t m, const double *__restrict__ d, double *w) {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < m) w[i] = d[i] * w[i];
-}
-
-__global__ void k_divide(int32_t m, const double *w, double nw, double *v) {
-    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) v[i] = w[i] / nw;
 }
 
 // global coarse id of each node's aggregate; -1 for a node MIS removed
@@ -271,46 +226,6 @@ __global__ void k_split_fill(int32_t m, const int32_t *__restrict__ ci, const in
         else { oj[po] = cj[k] - nloc; oa[po] = ca[k]; ++po; }
     }
 }
-
-// V-cycle vector passes (ksp.hip's, with CG's stop flag)
-__global__ __launch_bounds__(256) void k_mg_jacobi(int64_t n, const double *__restrict__ dinv,
-                                                   const double *__restrict__ b, double *x, const int *stop) {
-    if (stop && *stop) return;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        x[i] = dinv[i] * b[i];
-}
-
-__global__ __launch_bounds__(256) void k_mg_resid(int64_t n, const double *__restrict__ b, double *r,
-                                                  const int *stop) {
-    if (stop && *stop) return;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        r[i] = b[i] + (-1.0) * r[i];
-}
-
-__global__ __launch_bounds__(256) void k_mg_richardson(int64_t n, const double *__restrict__ dinv,
-                                                       const double *__restrict__ b, const double *__restrict__ ax,
-                                                       double *x, const int *stop) {
-    if (stop && *stop) return;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        x[i] = x[i] + 1.0 * (dinv[i] * (b[i] + (-1.0) * ax[i]));
-}
-
-// y[o] = y[o] + scale[o] * (-(A_o g)_o) over A_o's rows (scale NULL: 1): the
-// off-diagonal block's share of a fused residual (r = b - A_d x - A_o g) or
-// post-smoothing (x = t + D^-1 (b - A_d t - A_o g)) on the boundary rows
-__global__ __launch_bounds__(256) void k_offdiag_axpy(int32_t nr, const int32_t *__restrict__ rai,
-                                                      const int32_t *__restrict__ ridx, const int32_t *__restrict__ aj,
-                                                      const double *__restrict__ aa, const double *__restrict__ g,
-                                                      const double *__restrict__ scale, double *y, const int *stop) {
-    if (stop && *stop) return;
-    for (int32_t q = blockIdx.x * 256 + threadIdx.x; q < nr; q += gridDim.x * 256) {
-        const int32_t o = ridx ? ridx[q] : q;
-        double sum = 0.0;
-        for (int32_t k = rai[q]; k < rai[q + 1]; ++k) sum += aa[k] * g[aj[k]];
-        y[o] = y[o] + (scale ? scale[o] : 1.0) * (-sum);
-    }
-}
-
 
 // ---- PETSc's parallel MIS (mis.c maxIndSetAgg over an MPIAIJ graph: ghost
 // states exchanged every round), restated as the lexicographically-first
@@ -1298,10 +1213,10 @@ void Hierarchy::destroy() {
         }
         aijhip_mat_destroy(L.Pd);
         aijhip_mat_destroy(L.Po);
-        aijhip_mat_destroy(L.Ro);
         hipFree(L.dinv); hipFree(L.b); hipFree(L.x); hipFree(L.r);
     }
     lv.clear();
+    view.clear();
 }
 
 // The p2p halo plan of a level from its sorted ghost list: requests to the
@@ -1360,7 +1275,7 @@ struct PJob {
                 rc = e != hipSuccess ? gerr(e, "P^T") : aijhip::attach_transpose(Pd, ti, tj, ta);
             }
             if (!rc && po.nz > 0) rc = aijhip_gamg::make_level_handle(device, po, &Po);
-            if (!rc && Po) {  // P_o^T for the restriction's off-rank share (vcycle)
+            if (!rc && Po) {  // P_o^T for the restriction's off-rank share (mg_cycle.hip restrict_to)
                 int32_t *ti = nullptr, *tj = nullptr;
                 double *ta = nullptr;
                 const hipError_t e = aijhip::build_transpose(*Po, &ti, &tj, &ta, nullptr);
@@ -1482,7 +1397,7 @@ int build(aijhip_mpiaij *M0, const aijhip_gamg_params_t &p, Hierarchy &H) {
                     double rz = 0.0;
                     if (!emax_rc) {
                         if (m > 0)
-                            hipLaunchKernelGGL(k_cgest_start_off, dim3(nblk(m)), dim3(256), 0, nullptr, m, L.rstart,
+                            hipLaunchKernelGGL(k_cgest_start, dim3(nblk(m)), dim3(256), 0, nullptr, m, L.rstart,
                                                dinv_e, r, z, pv);
                         emax_rc = global_dot(C, z, r, m, part, &rz);
                     }
@@ -1516,10 +1431,10 @@ int build(aijhip_mpiaij *M0, const aijhip_gamg_params_t &p, Hierarchy &H) {
                     emax_rc = gerr(x, "alloc");
                 double nv = 0.0;
                 if (!emax_rc) {
-                    if (m > 0) hipLaunchKernelGGL(k_power_start_off, dim3(nblk(m)), dim3(256), 0, nullptr, m, L.rstart, v);
+                    if (m > 0) hipLaunchKernelGGL(k_power_start, dim3(nblk(m)), dim3(256), 0, nullptr, m, L.rstart, v);
                     emax_rc = global_norm(C, v, m, part, &nv);
                 }
-                if (!emax_rc && m > 0) hipLaunchKernelGGL(k_divide, dim3(nblk(m)), dim3(256), 0, nullptr, m, v, nv, v);
+                if (!emax_rc && m > 0) hipLaunchKernelGGL(k_div, dim3(nblk(m)), dim3(256), 0, nullptr, m, v, nv, v);
                 for (int it = 0; !emax_rc && it < p.eig_its; ++it) {
                     if ((emax_rc = aijhip_mpi::mpiaij_apply(L.op, v, w, nullptr, nullptr, nullptr, nullptr, false))) break;
                     if (m > 0) hipLaunchKernelGGL(k_scale_by, dim3(nblk(m)), dim3(256), 0, nullptr, m, dinv_e, w);
@@ -1527,7 +1442,7 @@ int build(aijhip_mpiaij *M0, const aijhip_gamg_params_t &p, Hierarchy &H) {
                     if ((emax_rc = global_norm(C, w, m, part, &nw))) break;
                     if (!(nw > 0.0)) break;
                     emax = nw;
-                    if (m > 0) hipLaunchKernelGGL(k_divide, dim3(nblk(m)), dim3(256), 0, nullptr, m, w, nw, v);
+                    if (m > 0) hipLaunchKernelGGL(k_div, dim3(nblk(m)), dim3(256), 0, nullptr, m, w, nw, v);
                 }
                 (void)hipStreamSynchronize(nullptr);
                 hipFree(v); hipFree(w); hipFree(part);
@@ -2080,6 +1995,18 @@ int build(aijhip_mpiaij *M0, const aijhip_gamg_params_t &p, Hierarchy &H) {
             hipLaunchKernelGGL(k_diag_inv, dim3(nblk(L.m)), dim3(256), 0, nullptr, L.m, L.Ad->d_ai, L.Ad->d_aj,
                                L.Ad->d_aa, L.dinv);
     }
+    // what the V-cycle walks (mg_cycle.h): the smoothing SpMVs fused with
+    // their vector passes on STREAM-planned blocks (launch_mg_resid / _post
+    // over A_d while the halo moves, then A_o's share on the boundary rows);
+    // AIJHIP_MG_UNFUSED=1 keeps PETSc's order, for A/B. No template D^-1 and
+    // no fused dots: CG's z.z / z.r come from k_dots on this hierarchy.
+    const bool unfused = std::getenv("AIJHIP_MG_UNFUSED") != nullptr;
+    for (size_t l = 0; !rc && l < H.lv.size(); ++l) {
+        Level &L = H.lv[l];
+        L.op_next = l + 1 < H.lv.size() ? H.lv[l + 1].op : nullptr;
+        L.fused = !unfused && aijhip::stream_mg_fusable(*L.Ad);
+        H.view.push_back(L);
+    }
     if (!rc && (e = hipDeviceSynchronize()) != hipSuccess) rc = gerr(e, "set-up");
     if (rc) H.destroy();
     return rc;
@@ -2129,108 +2056,6 @@ int get_level(const Hierarchy &H, int32_t l, char which, int64_t *rstart, int32_
         return level_rows(L.Pd, L.Po, N.rstart, N.ghost_gid, ai, aj, aa);
     }
     return mfail(AIJHIP_ERR_ARG, "which: 'A' or 'P'");
-}
-
-// y = B x (+ z) through the halo of `halo_op`: the exchange of x overlaps B_d x
-static int transfer(aijhip_mpiaij *halo_op, const aijhip_mat *Bd, const aijhip_mat *Bo, const double *x,
-                    const double *z, double *y, bool add, hipStream_t s, const int *stop) {
-    const bool exch = halo_op->n_send > 0 || halo_op->n_ghost > 0;
-    int rc = exch ? aijhip_mpi::halo_post(halo_op, x, s) : AIJHIP_OK;
-    if (rc) return rc;
-    hipError_t e = aijhip::launch_mult(*Bd, x, z, y, add, s, stop);
-    if (e != hipSuccess)
-        return exch ? aijhip_mpi::halo_abort(halo_op, s, gerr(e, "transfer product")) : gerr(e, "transfer product");
-    if (exch && (rc = aijhip_mpi::halo_finish(halo_op, s))) return rc;
-    if (Bo && (e = aijhip::launch_mult(*Bo, halo_op->d_ghost, y, y, true, s, stop)) != hipSuccess)
-        return gerr(e, "transfer ghost product");
-    return AIJHIP_OK;
-}
-
-// MatRestrict as MatMultTranspose_MPIAIJ: b = P_d^T r, then P_o^T r (one
-// value per ghost coarse slot of level l+1, in that level's ghost vector)
-// sent back to the slots' owners and added (halo_reverse_add). An aggregate
-// may have members on other ranks up to two steps from its root (PETSc's
-// parallel MIS), and P's smoothing reaches one more, so the fine rows with
-// entries in a rank's coarse columns are not all ghosts of its level-l halo:
-// the sums travel with the coarse level's plan instead.
-static int restrict_to(const Level &L, Level &N, const double *r, double *b, hipStream_t s, const int *stop) {
-    hipError_t e = aijhip::launch_mult(*L.Pd->transpose, r, nullptr, b, false, s, stop);
-    if (e != hipSuccess) return gerr(e, "restriction");
-    aijhip_mpiaij *M = N.op;
-    if (M->n_send == 0 && M->n_ghost == 0) return AIJHIP_OK;
-    double *t = M->d_ghost;
-    if (L.Po && L.Po->transpose) e = aijhip::launch_mult(*L.Po->transpose, r, nullptr, t, false, s, stop);
-    else if (M->n_ghost > 0) e = hipMemsetAsync(t, 0, sizeof(double) * (size_t)M->n_ghost, s);
-    if (e != hipSuccess) return gerr(e, "restriction (off-rank share)");
-    return aijhip_mpi::halo_reverse_add(M, t, b, s);
-}
-
-// The A_o correction of a fused smoothing launch (after the halo landed).
-static int offdiag_axpy(const Level &L, const double *scale, double *y, hipStream_t s, const int *stop) {
-    if (!L.Ao) return AIJHIP_OK;
-    const aijhip::RowList R = aijhip::row_list(*L.Ao);
-    if (R.nr == 0) return AIJHIP_OK;
-    hipLaunchKernelGGL(k_offdiag_axpy, dim3(nblk(R.nr)), dim3(256), 0, s, R.nr, R.rai, R.ridx, L.Ao->d_aj,
-                       L.Ao->d_aa, L.op->d_ghost, scale, y, stop);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? AIJHIP_OK : gerr(e, "off-diagonal smoothing share");
-}
-
-int vcycle(Hierarchy &H, const double *b0, double *x0, hipStream_t s, const int *stop) {
-    const int nl = (int)H.lv.size();
-    auto B = [&](int l) { return l == 0 ? b0 : (const double *)H.lv[l].b; };
-    auto X = [&](int l) { return l == 0 ? x0 : H.lv[l].x; };
-    auto grid = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 2048))); };
-    // smoothing SpMVs fused with their vector passes on STREAM-planned blocks
-    // (ksp.hip's launch_mg_resid / launch_mg_post over A_d while the halo
-    // moves, then A_o's share on the boundary rows); AIJHIP_MG_UNFUSED=1 for A/B
-    static const bool unfused = std::getenv("AIJHIP_MG_UNFUSED") != nullptr;
-    auto fused = [&](const Level &L) { return !unfused && aijhip::stream_mg_fusable(*L.Ad); };
-    auto exchanges = [](const aijhip_mpiaij *M) { return M->n_send > 0 || M->n_ghost > 0; };
-    int rc;
-    hipError_t e;
-    for (int l = 0; l < nl; ++l) {
-        Level &L = H.lv[l];
-        hipLaunchKernelGGL(k_mg_jacobi, grid(L.m), dim3(256), 0, s, (int64_t)L.m, L.dinv, B(l), X(l), stop);
-        if (l == nl - 1) break;  // coarse: preonly + Jacobi
-        // r = b - A x
-        if (fused(L)) {
-            const bool ex = exchanges(L.op);
-            if (ex && (rc = aijhip_mpi::halo_post(L.op, X(l), s))) return rc;
-            if ((e = aijhip::launch_mg_resid(*L.Ad, X(l), B(l), L.r, s, stop)) != hipSuccess)
-                return ex ? aijhip_mpi::halo_abort(L.op, s, gerr(e, "residual")) : gerr(e, "residual");
-            if (ex && (rc = aijhip_mpi::halo_finish(L.op, s))) return rc;
-            if ((rc = offdiag_axpy(L, nullptr, L.r, s, stop))) return rc;
-        } else {  // MatMult_MPIAIJ, then the residual
-            if ((rc = aijhip_mpi::mpiaij_apply(L.op, X(l), L.r, s, nullptr, nullptr, nullptr, false, stop))) return rc;
-            hipLaunchKernelGGL(k_mg_resid, grid(L.m), dim3(256), 0, s, (int64_t)L.m, B(l), L.r, stop);
-        }
-        // MatRestrict: b_{l+1} = P^T r = P_d^T r + R_o r_ghost
-        if ((rc = restrict_to(L, H.lv[l + 1], L.r, H.lv[l + 1].b, s, stop))) return rc;
-    }
-    for (int l = nl - 2; l >= 0; --l) {
-        Level &L = H.lv[l];
-        if (fused(L)) {
-            // MatInterpolateAdd into the scratch: t = x + P x_c, then smoothu
-            // x = t + D^-1 (b - A t) in the SpMV epilogue over A_d
-            if ((rc = transfer(H.lv[l + 1].op, L.Pd, L.Po, X(l + 1), X(l), L.r, true, s, stop))) return rc;
-            const bool ex = exchanges(L.op);
-            if (ex && (rc = aijhip_mpi::halo_post(L.op, L.r, s))) return rc;
-            if ((e = aijhip::launch_mg_post(*L.Ad, L.r, B(l), L.dinv, X(l), nullptr, s, stop)) != hipSuccess)
-                return ex ? aijhip_mpi::halo_abort(L.op, s, gerr(e, "post-smoothing")) : gerr(e, "post-smoothing");
-            if (ex && (rc = aijhip_mpi::halo_finish(L.op, s))) return rc;
-            if ((rc = offdiag_axpy(L, L.dinv, X(l), s, stop))) return rc;
-        } else {
-            // MatInterpolateAdd: x = x + P x_c (P_d x_c + P_o x_c ghost)
-            if ((rc = transfer(H.lv[l + 1].op, L.Pd, L.Po, X(l + 1), X(l), X(l), true, s, stop))) return rc;
-            // smoothu: x = x + D^-1 (b - A x)
-            if ((rc = aijhip_mpi::mpiaij_apply(L.op, X(l), L.r, s, nullptr, nullptr, nullptr, false, stop))) return rc;
-            hipLaunchKernelGGL(k_mg_richardson, grid(L.m), dim3(256), 0, s, (int64_t)L.m, L.dinv, B(l), L.r, X(l),
-                               stop);
-        }
-    }
-    e = hipGetLastError();
-    return e == hipSuccess ? AIJHIP_OK : gerr(e, "V-cycle");
 }
 
 }  // namespace aijhip_gamg_mpi

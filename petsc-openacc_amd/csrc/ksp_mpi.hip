@@ -39,9 +39,10 @@
 
 #include "aijhip_internal.h"
 #include "aijhip_mpi.h"
-#include "cg_device.h"
+#include "cg_solve.h"
 #include "gamg_device.h"
 #include "gamg_mpi.h"
+#include "mg_cycle.h"
 #include "mpi_internal.h"
 
 namespace aijhip_mpi {
@@ -61,15 +62,6 @@ int mhip(hipError_t e, const char *what) {
 using namespace aijhip_mpi;
 
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        int cur = -1;
-        if (hipGetDevice(&cur) == hipSuccess && cur != dev && hipSetDevice(dev) == hipSuccess) prev = cur;
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // ------------------------------------------------------------ RCCL table
 struct Rccl {
@@ -372,66 +364,6 @@ __global__ __launch_bounds__(kVecThreads) void k_offdiag(int32_t nr, const int32
     if (!part) return;
     const double v = bsum<kVecThreads>(d, scratch);
     if (threadIdx.x == 0) part[blockIdx.x] = v;
-}
-
-// red[q] = this device's fixed-order sum of part[q*nb .. (q+1)*nb), q < nq
-// (the single-GPU solver's k_reduce_* sums). step: one rank, no all-reduce
-// in between — apply the scalar step here (1: init, 2: iteration) as the
-// single-GPU solver's fused reduce kernels do.
-__global__ __launch_bounds__(kRedThreads) void k_local_sums(const double *part, int nb, int nq, double *red,
-                                                            int step, CGState *S, double *hist, CGParams p) {
-    __shared__ double scratch[kRedThreads / 64];
-    if (step == 2 && S->done) return;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int q = 0; q < nq; ++q) v[q] = reduce_parts(part + (size_t)q * nb, nb, scratch);
-    if (threadIdx.x != 0) return;
-    if (step == 1) step_init(v[0], v[1], v[2], v[3], S, hist, p);
-    else if (step == 2) step_iter(v[0], v[1], v[2], S, hist, p);
-    else for (int q = 0; q < nq; ++q) red[q] = v[q];
-}
-
-// dpi's local sum: the A_d epilogue's partials, then the A_o corrections
-// (step: apply step_dpi here, one rank).
-__global__ __launch_bounds__(kRedThreads) void k_local_dpi(const double *part, int nb, const double *opart,
-                                                           int nob, double *red, CGState *S, int step) {
-    __shared__ double scratch[kRedThreads / 64];
-    if (S->done) return;
-    double v = reduce_parts(part, nb, scratch);
-    if (nob > 0) {
-        const double o = reduce_parts(opart, nob, scratch);
-        v += o;
-    }
-    if (threadIdx.x != 0) return;
-    if (step) step_dpi(v, S);
-    else red[0] = v;
-}
-
-// GAMG sub-PC: zz, zr from pz[0, nbz) and pz[nbz, 2 nbz) (the V-cycle's fused
-// finest post-smoothing, or k_dots), rr from pr[0, nbr) — ksp.hip
-// k_reduce_iter's sums; step: apply step_iter here (one rank).
-__global__ __launch_bounds__(kRedThreads) void k_local_iter(const double *pz, int nbz, const double *pr, int nbr,
-                                                            double *red, int step, CGState *S, double *hist,
-                                                            CGParams p) {
-    __shared__ double scratch[kRedThreads / 64];
-    if (S->done) return;
-    const double zz = reduce_parts(pz, nbz, scratch);
-    const double zr = reduce_parts(pz + nbz, nbz, scratch);
-    const double rr = reduce_parts(pr, nbr, scratch);
-    if (threadIdx.x != 0) return;
-    if (step) step_iter(zz, zr, rr, S, hist, p);
-    else { red[0] = zz; red[1] = zr; red[2] = rr; }
-}
-
-__global__ void k_step_init(const double *red, CGState *S, double *hist, CGParams p) {
-    if (threadIdx.x == 0) step_init(red[0], red[1], red[2], red[3], S, hist, p);
-}
-
-__global__ void k_step_dpi(const double *red, CGState *S) {
-    if (threadIdx.x == 0 && !S->done) step_dpi(red[0], S);
-}
-
-__global__ void k_step_iter(const double *red, CGState *S, double *hist, CGParams p) {
-    if (threadIdx.x == 0 && !S->done) step_iter(red[0], red[1], red[2], S, hist, p);
 }
 
 int grid_of(int64_t n, int cap) {
@@ -742,12 +674,9 @@ int mpiaij_apply(aijhip_mpiaij *M, const double *x, double *y, hipStream_t s, do
 
 struct aijhip_kspmpi {
     aijhip_mpiaij *M = nullptr;
-    double rtol = 1e-5, abstol = 1e-50, dtol = 1e5;
-    int32_t max_it = 10000;
-    int pc = AIJHIP_PC_JACOBI;
-    int normtype = AIJHIP_KSP_NORM_PRECONDITIONED;
-    int32_t poll = 8;
-    bool set_up = false, fused = false;
+    CGSolve cg;  // the tolerances, CG's vectors, the last solve's results (cg_solve.h)
+    int32_t host_syncs = 0;  // host waits of the last solve (polls, host-transport collectives)
+    bool set_up = false;
     // the blocks' plan and values generations at set-up: new values or a
     // re-plan (on every rank: MatAssemblyEnd is collective) redo the set-up,
     // as PETSc's PCSetUp does when the operator's state changed
@@ -761,15 +690,7 @@ struct aijhip_kspmpi {
     double setup_seconds = 0.0;
     aijhip_gamg_params_t gamg{};
     bool gamg_set = false;
-    int vec_grid = 1, n_dparts = 1;
-    double *d_dinv = nullptr, *d_r = nullptr, *d_z = nullptr, *d_p = nullptr, *d_part = nullptr,
-           *d_opart = nullptr, *d_red = nullptr, *d_hist = nullptr;
-    int32_t hist_cap = 0;
-    CGState *d_state = nullptr, *h_state = nullptr;
-    int32_t its = 0, host_syncs = 0;
-    int reason = 0;
-    double rnorm = 0.0;
-    std::vector<double> hist;
+    double *d_opart = nullptr;  // A_o's p.w correction partials (k_offdiag)
     // The poll batch (poll iterations) captured once into a HIP graph and
     // replayed by one hipGraphLaunch (aijhip_kspmpi_set_graph): the RCCL
     // enqueues of the halo and the all-reduces (15-25 us of host time per
@@ -790,9 +711,9 @@ void kspmpi_free(aijhip_kspmpi *K) {
     if (K->gexec) (void)hipGraphExecDestroy(K->gexec);
     K->gexec = nullptr;
     K->g_x = nullptr;
-    hipFree(K->d_dinv); hipFree(K->d_r); hipFree(K->d_z); hipFree(K->d_p); hipFree(K->d_part);
-    hipFree(K->d_opart); hipFree(K->d_red); hipFree(K->d_hist); hipFree(K->d_state);
-    if (K->h_state) hipHostFree(K->h_state);
+    cg_free(K->cg);
+    hipFree(K->d_opart);
+    K->d_opart = nullptr;
     if (K->sub) aijhip_ksp_destroy(K->sub);
     K->sub = nullptr;
     if (K->dh) {
@@ -800,8 +721,6 @@ void kspmpi_free(aijhip_kspmpi *K) {
         delete K->dh;
         K->dh = nullptr;
     }
-    K->d_dinv = K->d_r = K->d_z = K->d_p = K->d_part = K->d_opart = K->d_red = K->d_hist = nullptr;
-    K->d_state = K->h_state = nullptr;
     K->set_up = false;
 }
 
@@ -820,58 +739,32 @@ int kspmpi_set_up(aijhip_kspmpi *K) {
     kspmpi_free(K);
     aijhip_mpiaij *M = K->M;
     aijhip_mat *A = M->Ad;
-    const int64_t m = A->m;
-    K->fused = aijhip::stream_dot_fusable(*A);
-    K->vec_grid = (int)std::max<int64_t>(1, std::min<int64_t>((m + kVecThreads - 1) / kVecThreads,
-                                                              (int64_t)A->n_cu * 8));
-    K->n_dparts = K->fused ? std::max(1, A->plan.n_blocks) : K->vec_grid;
-    const int64_t nparts = std::max<int64_t>((int64_t)kNQ * K->vec_grid, K->n_dparts);
-    K->hist_cap = K->max_it + 2;
-    const size_t vb = sizeof(double) * (size_t)std::max<int64_t>(m, 1);
+    const int pc = K->cg.pc;
+    // explicit Z for now: implicit Z (Jacobi on row templates) is this flag
+    int rc = cg_set_up(K->cg, *A, false);
     hipError_t e;
-    if ((e = hipMalloc(&K->d_dinv, vb)) != hipSuccess || (e = hipMalloc(&K->d_r, vb)) != hipSuccess ||
-        (e = hipMalloc(&K->d_z, vb)) != hipSuccess || (e = hipMalloc(&K->d_p, vb)) != hipSuccess ||
-        (e = hipMalloc(&K->d_part, sizeof(double) * (size_t)nparts)) != hipSuccess ||
-        (e = hipMalloc(&K->d_opart, sizeof(double) * (size_t)M->o_grid)) != hipSuccess ||
-        (e = hipMalloc(&K->d_red, sizeof(double) * 8)) != hipSuccess ||
-        (e = hipMalloc(&K->d_hist, sizeof(double) * (size_t)K->hist_cap)) != hipSuccess ||
-        (e = hipMalloc(&K->d_state, sizeof(CGState))) != hipSuccess ||
-        (e = hipHostMalloc(&K->h_state, sizeof(CGState), hipHostMallocDefault)) != hipSuccess) {
-        kspmpi_free(K);
-        return mhip(e, "KSPSetUp (distributed) allocation");
-    }
-    if (m > 0) {
-        hipLaunchKernelGGL(k_diag_inv, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, nullptr, A->m, A->d_ai,
-                           A->d_aj, A->d_aa, K->d_dinv);
-        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
-            kspmpi_free(K);
-            return mhip(e, "PCSetUp_Jacobi (distributed)");
-        }
-    }
+    if (!rc && (e = hipMalloc(&K->d_opart, sizeof(double) * (size_t)M->o_grid)) != hipSuccess)
+        rc = mhip(e, "KSPSetUp (distributed) allocation");
     // GAMG across ranks: more than one rank (AIJHIP_GAMG_DIST=1 forces the
     // distributed set-up at one rank too, for tests)
     const char *force = std::getenv("AIJHIP_GAMG_DIST");
-    const bool dist = K->pc == AIJHIP_PC_GAMG && (M->comm->nranks > 1 || (force && std::atoi(force) != 0));
-    if (dist) {
+    const bool dist = pc == AIJHIP_PC_GAMG && (M->comm->nranks > 1 || (force && std::atoi(force) != 0));
+    if (!rc && dist) {
         aijhip_gamg_params_t gp;
         if (K->gamg_set) gp = K->gamg;
         else aijhip_gamg_params_default(&gp);
         K->dh = new (std::nothrow) aijhip_gamg_mpi::Hierarchy();
-        int rc = K->dh ? aijhip_gamg_mpi::build(M, gp, *K->dh) : mfail(AIJHIP_ERR_ALLOC, "host allocation");
-        if (rc) {
-            kspmpi_free(K);
-            return rc;
-        }
-    } else if (K->pc == AIJHIP_PC_GAMG || K->pc == AIJHIP_PC_BJACOBI_GAMG) {
+        rc = K->dh ? aijhip_gamg_mpi::build(M, gp, *K->dh) : mfail(AIJHIP_ERR_ALLOC, "host allocation");
+    } else if (!rc && (pc == AIJHIP_PC_GAMG || pc == AIJHIP_PC_BJACOBI_GAMG)) {
         // PCSetUp_BJacobi + the sub-PC's PCSetUp_GAMG on A_d (at one rank: PCGAMG itself)
-        int rc = aijhip_ksp_create(A, &K->sub);
+        rc = aijhip_ksp_create(A, &K->sub);
         if (!rc) rc = aijhip_ksp_set_pc_type(K->sub, AIJHIP_PC_GAMG);
         if (!rc && K->gamg_set) rc = aijhip_ksp_set_gamg_params(K->sub, &K->gamg);
         if (!rc) rc = aijhip_ksp_set_up(K->sub);
-        if (rc) {
-            kspmpi_free(K);
-            return rc;
-        }
+    }
+    if (rc) {
+        kspmpi_free(K);
+        return rc;
     }
     K->setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count();
     K->set_up = true;
@@ -879,17 +772,89 @@ int kspmpi_set_up(aijhip_kspmpi *K) {
     return AIJHIP_OK;
 }
 
-// z = B r with the GAMG PC: the distributed hierarchy or the per-rank one.
-// *dots: the fused finest post-smoothing's z.z / z.r partials, or NULL.
-// stop: CG's flag, NULL for the V-cycle before the first scalar step (the
-// device state is initialised by that step).
-int pc_gamg_apply(aijhip_kspmpi *K, hipStream_t s, const double **dots, int *nbz, const int *stop) {
-    *dots = nullptr;
-    *nbz = 0;
-    if (K->dh) return aijhip_gamg_mpi::vcycle(*K->dh, K->d_r, K->d_z, s, stop);
-    const hipError_t e = aijhip::ksp_pc_vcycle(K->sub, K->d_r, K->d_z, s, dots, nbz, stop);
-    return e == hipSuccess ? AIJHIP_OK : mhip(e, "GAMG V-cycle");
-}
+// What the distributed handle plugs into the CG driver: MatMult_MPIAIJ, the
+// all-reduce of the communicator, the distributed hierarchy's V-cycle or the
+// per-rank one, wait_stream, and the poll batch as a captured HIP graph.
+struct MpiOperator final : CGOperator {
+    aijhip_kspmpi *K;
+    aijhip_mpiaij *M;
+    aijhip_comm *C;
+    explicit MpiOperator(aijhip_kspmpi *k) : K(k), M(k->M), C(k->M->comm) {
+        multi = C->nranks > 1;
+        vcycle = K->cg.pc == AIJHIP_PC_GAMG || K->cg.pc == AIJHIP_PC_BJACOBI_GAMG;
+        // The A_o correction partials (p_o w_o(new) - p_o w_o(old)) complete p.w
+        // only when the A_d epilogue summed p_o w_o(old), i.e. in the fused path;
+        // otherwise k_dot sums p.w over the final w and the A_o rows are already
+        // in it (counting them twice broke conjugacy).
+        const bool have_o = M->Ao && aijhip::row_list(*M->Ao).nr > 0;
+        opart = (have_o && K->cg.fused) ? K->d_opart : nullptr;
+        nob = opart ? M->o_grid : 0;
+    }
+    int apply(const double *x, double *y, hipStream_t s, double *part, const CGState *S) override {
+        return mpiaij_apply(M, x, y, s, part, part ? opart : nullptr, S, part && K->cg.fused);
+    }
+    int allreduce(double *red, int n, hipStream_t s) override { return comm_allreduce(C, red, n, s); }
+    // z = B r with the GAMG PC: the distributed hierarchy (no fused dots: its
+    // finest post-smoothing is completed by A_o's share) or the per-rank one
+    int pc_apply(const double *r, double *z, hipStream_t s, const int *stop, const double **dots,
+                 int *nbz) override {
+        if (!K->dh) return aijhip::ksp_pc_vcycle(K->sub, r, z, s, stop, dots, nbz);
+        if (dots) *dots = nullptr;
+        return aijhip::mg_vcycle(K->dh->view, r, z, s, stop);
+    }
+    int wait(hipStream_t s) override { return wait_stream(C, s); }
+    // The poll batch as a HIP graph: RCCL only (the host transport waits on
+    // the host inside the exchanges), full batches only; captured on the
+    // handle's own stream and re-captured when what it baked in changes (x,
+    // the batch length, the tolerances and norm, the set-up)
+    int run_batch(const CGRun &R, int32_t n, hipStream_t s) override {
+        const bool use_graph = C->kind == AIJHIP_COMM_RCCL && K->graph == 1;  // (-1: the default, off)
+        if (!use_graph || n < K->cg.poll) return CGOperator::run_batch(R, n, s);
+        static const bool gdbg = std::getenv("AIJHIP_GRAPH_DEBUG") != nullptr;
+        auto dbg = [&](const char *what) {
+            if (gdbg) std::fprintf(stderr, "[kspmpi graph, rank %d] %s\n", C->rank, what);
+        };
+        const CGParams &p = R.p;
+        uint64_t key = 1469598103934665603ULL;
+        for (double v : {p.rtol, p.abstol, p.dtol})
+            key = (key ^ std::hash<double>{}(v)) * 1099511628211ULL;
+        key = (key ^ (uint64_t)(uint32_t)p.max_it ^ ((uint64_t)(uint32_t)p.normtype << 32) ^
+               ((uint64_t)(uint32_t)p.pc << 40)) * 1099511628211ULL;
+        key = (key ^ K->gens[0] ^ (K->gens[1] << 1) ^ (K->gens[2] << 2) ^ (K->gens[3] << 3) ^
+               (uint64_t)(uintptr_t)K->cg.d_state) * 1099511628211ULL;
+        hipError_t e;
+        if (!K->gexec || K->g_x != R.x || K->g_poll != n || K->g_key != key) {
+            if (K->gexec) (void)hipGraphExecDestroy(K->gexec);
+            K->gexec = nullptr;
+            if (!K->gs && (e = hipStreamCreateWithFlags(&K->gs, hipStreamNonBlocking)) != hipSuccess)
+                return mhip(e, "KSPSolve capture stream");
+            dbg("begin capture");
+            if ((e = hipStreamBeginCapture(K->gs, hipStreamCaptureModeRelaxed)) != hipSuccess)
+                return mhip(e, "KSPSolve capture");
+            aijhip_mpi::g_capturing = true;
+            const int crc = CGOperator::run_batch(R, n, K->gs);
+            aijhip_mpi::g_capturing = false;
+            hipGraph_t graph = nullptr;
+            e = hipStreamEndCapture(K->gs, &graph);
+            dbg(e == hipSuccess ? "end capture" : "end capture failed");
+            if (!crc && e == hipSuccess) e = hipGraphInstantiate(&K->gexec, graph, nullptr, nullptr, 0);
+            dbg(e == hipSuccess ? "instantiated" : "instantiate failed");
+            if (graph) (void)hipGraphDestroy(graph);
+            if (crc) return crc;
+            if (e != hipSuccess) {
+                K->gexec = nullptr;
+                return mhip(e, "KSPSolve capture (end / instantiate)");
+            }
+            K->g_x = R.x;
+            K->g_poll = n;
+            K->g_key = key;
+        }
+        if ((e = hipGraphLaunch(K->gexec, s)) != hipSuccess) return mhip(e, "KSPSolve graph launch");
+        dbg("batch launched");
+        ++K->graph_batches;
+        return AIJHIP_OK;
+    }
+};
 
 }  // namespace
 
@@ -1158,20 +1123,10 @@ int aijhip_kspmpi_create(aijhip_mpiaij_t M, aijhip_kspmpi_t *out) {
 
 int aijhip_kspmpi_set_tolerances(aijhip_kspmpi_t K, double rtol, double abstol, double dtol, int32_t max_it) {
     if (!K) return mfail(AIJHIP_ERR_ARG, "NULL ksp");
-    if (rtol < 0 || abstol < 0 || dtol <= 0 || max_it < 0) return mfail(AIJHIP_ERR_ARG, "bad tolerance");
-    K->rtol = rtol; K->abstol = abstol; K->dtol = dtol;
-    K->max_it = max_it;
-    if (K->set_up && max_it + 2 > K->hist_cap) {  // regrow the history only (keeps dinv and the sub-PC)
-        DeviceGuard g(K->M->comm->device);
-        hipFree(K->d_hist);
-        K->d_hist = nullptr;
-        K->hist_cap = max_it + 2;
-        if (hipMalloc(&K->d_hist, sizeof(double) * (size_t)K->hist_cap) != hipSuccess) {
-            K->set_up = false;
-            return mfail(AIJHIP_ERR_ALLOC, "residual history");
-        }
-    }
-    return AIJHIP_OK;
+    DeviceGuard g(K->M->comm->device);
+    const int rc = cg_set_tolerances(K->cg, K->set_up, rtol, abstol, dtol, max_it);
+    if (rc == AIJHIP_ERR_ALLOC) K->set_up = false;
+    return rc;
 }
 
 int aijhip_kspmpi_set_pc_type(aijhip_kspmpi_t K, int pc) {
@@ -1186,8 +1141,8 @@ int aijhip_kspmpi_set_pc_type(aijhip_kspmpi_t K, int pc) {
                      "PC gamg across ranks needs the operator's p2p halo: create a p2p twin of this all-gather "
                      "operator sharing A_d (aijhip_mpiaij_create with AIJHIP_HALO_P2P; mpiaij.MPIAIJ.p2p_native()), "
                      "or use AIJHIP_PC_BJACOBI_GAMG");
-    if (pc != K->pc) K->set_up = false;
-    K->pc = pc;
+    if (pc != K->cg.pc) K->set_up = false;
+    K->cg.pc = pc;
     if (pc == AIJHIP_PC_GAMG || pc == AIJHIP_PC_BJACOBI_GAMG)  // the set-up's streams, made once per process
         for (int slot = 0; slot < 2; ++slot) (void)aijhip_gamg::setup_stream(K->M->comm->device, slot);
     return AIJHIP_OK;
@@ -1197,20 +1152,20 @@ int aijhip_kspmpi_set_gamg_params(aijhip_kspmpi_t K, const aijhip_gamg_params_t 
     if (!K) return mfail(AIJHIP_ERR_ARG, "NULL ksp");
     K->gamg_set = p != nullptr;
     if (p) K->gamg = *p;
-    if (K->pc == AIJHIP_PC_GAMG) K->set_up = false;
+    if (K->cg.pc == AIJHIP_PC_GAMG) K->set_up = false;
     return AIJHIP_OK;
 }
 
 int aijhip_kspmpi_set_norm_type(aijhip_kspmpi_t K, int nt) {
     if (!K) return mfail(AIJHIP_ERR_ARG, "NULL ksp");
     if (nt < AIJHIP_KSP_NORM_NONE || nt > AIJHIP_KSP_NORM_NATURAL) return mfail(AIJHIP_ERR_ARG, "bad norm type");
-    K->normtype = nt;
+    K->cg.normtype = nt;
     return AIJHIP_OK;
 }
 
 int aijhip_kspmpi_set_poll_interval(aijhip_kspmpi_t K, int32_t iters) {
     if (!K || iters < 1) return mfail(AIJHIP_ERR_ARG, "bad poll interval");
-    K->poll = iters;
+    K->cg.poll = iters;
     return AIJHIP_OK;
 }
 
@@ -1229,189 +1184,40 @@ int aijhip_kspmpi_get_graph_batches(aijhip_kspmpi_t K, int32_t *batches) {
 int aijhip_kspmpi_solve(aijhip_kspmpi_t K, const double *b, double *x, void *stream) {
     aijhip::Range range("KSPSolve (MPIAIJ)");
     if (!K) return mfail(AIJHIP_ERR_ARG, "NULL ksp");
-    aijhip_mpiaij *M = K->M;
-    aijhip_comm *C = M->comm;
+    aijhip_comm *C = K->M->comm;
     DeviceGuard g(C->device);
     int rc = kspmpi_set_up(K);
     if (rc) return rc;
-    const int64_t m = M->mloc;
-    if (m > 0 && (!b || !x)) return mfail(AIJHIP_ERR_ARG, "NULL vector");
-    if (b == x) return mfail(AIJHIP_ERR_ARG, "b and x alias");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool multi = C->nranks > 1;
-    CGParams p{K->rtol, K->abstol, K->dtol, K->max_it, K->normtype, 1, K->pc};
-    const dim3 vg(K->vec_grid), vt(kVecThreads), rt(kRedThreads);
-    const int nb = K->vec_grid;
-    const double *dinv = K->pc == AIJHIP_PC_JACOBI ? K->d_dinv : nullptr;
     const int64_t waits0 = C->waits;
-    hipError_t e = hipSuccess;
-    if (m > 0 && (e = hipMemsetAsync(x, 0, sizeof(double) * (size_t)m, s)) != hipSuccess) return mhip(e, "x = 0");
-    // r = b, z = B r, then ||z|| etc. summed over all ranks
-    const bool gamg = K->pc == AIJHIP_PC_GAMG || K->pc == AIJHIP_PC_BJACOBI_GAMG;
-    hipLaunchKernelGGL(k_init, vg, vt, 0, s, m, b, K->d_r, K->d_z, dinv, K->d_part, p);
-    if (gamg) {  // z = B r, then its z.z, z.r partials (as ksp.hip with a zero guess)
-        const double *dots = nullptr;
-        int nbz = 0;
-        if ((rc = pc_gamg_apply(K, s, &dots, &nbz, nullptr))) return rc;
-        hipLaunchKernelGGL(k_dots, vg, vt, 0, s, m, K->d_z, K->d_r, K->d_part, 0, 1, nullptr);
-    }
-    hipLaunchKernelGGL(k_local_sums, dim3(1), rt, 0, s, K->d_part, nb, 4, K->d_red, multi ? 0 : 1, K->d_state,
-                       K->d_hist, p);
-    if (multi) {
-        if ((rc = comm_allreduce(C, K->d_red, 4, s))) return rc;
-        hipLaunchKernelGGL(k_step_init, dim3(1), dim3(64), 0, s, K->d_red, K->d_state, K->d_hist, p);
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return mhip(e, "KSPSolve init");
-    const bool have_o = M->Ao && aijhip::row_list(*M->Ao).nr > 0;
-    // The A_o correction partials (p_o w_o(new) - p_o w_o(old)) complete p.w
-    // only when the A_d epilogue summed p_o w_o(old), i.e. in the fused path;
-    // otherwise k_dot sums p.w over the final w and the A_o rows are already
-    // in it (counting them twice broke conjugacy).
-    double *opart = (have_o && K->fused) ? K->d_opart : nullptr;
-    const int nob = opart ? M->o_grid : 0;
-    // one CG iteration on stream st (every kernel returns at once past the
-    // device stop flag; every collective is issued on every rank regardless)
-    auto iteration = [&](hipStream_t st) -> int {
-        int r;
-        hipLaunchKernelGGL(k_aypx<true>, vg, vt, 0, st, m, K->d_z, K->d_p, x, K->d_state);
-        // W = A P with the p.w partials (W shares Z's storage)
-        if ((r = mpiaij_apply(M, K->d_p, K->d_z, st, K->d_part, opart, K->d_state, K->fused))) return r;
-        if (!K->fused) hipLaunchKernelGGL(k_dot, vg, vt, 0, st, m, K->d_p, K->d_z, K->d_part, K->d_state);
-        hipLaunchKernelGGL(k_local_dpi, dim3(1), rt, 0, st, K->d_part, K->n_dparts, opart, nob, K->d_red,
-                           K->d_state, multi ? 0 : 1);
-        if (multi) {
-            if ((r = comm_allreduce(C, K->d_red, 1, st))) return r;
-            hipLaunchKernelGGL(k_step_dpi, dim3(1), dim3(64), 0, st, K->d_red, K->d_state);
-        }
-        hipLaunchKernelGGL(k_update<true>, vg, vt, 0, st, m, K->d_r, K->d_z, dinv, K->d_part, K->d_state, K->pc,
-                           K->d_p, nullptr);
-        if (gamg) {  // z = B r; z.z and z.r from the fused finest post-smoothing, else k_dots
-            const double *dots = nullptr;
-            int nbz = 0;
-            if ((r = pc_gamg_apply(K, st, &dots, &nbz, &K->d_state->done))) return r;
-            if (!dots) {
-                hipLaunchKernelGGL(k_dots, vg, vt, 0, st, m, K->d_z, K->d_r, K->d_part, 0, 1, K->d_state);
-                dots = K->d_part;
-                nbz = nb;
-            }
-            hipLaunchKernelGGL(k_local_iter, dim3(1), rt, 0, st, dots, nbz, K->d_part + 2 * nb, nb, K->d_red,
-                               multi ? 0 : 1, K->d_state, K->d_hist, p);
-        } else {
-            hipLaunchKernelGGL(k_local_sums, dim3(1), rt, 0, st, K->d_part, nb, 3, K->d_red, multi ? 0 : 2,
-                               K->d_state, K->d_hist, p);
-        }
-        if (multi) {
-            if ((r = comm_allreduce(C, K->d_red, 3, st))) return r;
-            hipLaunchKernelGGL(k_step_iter, dim3(1), dim3(64), 0, st, K->d_red, K->d_state, K->d_hist, p);
-        }
-        const hipError_t le = hipGetLastError();
-        return le == hipSuccess ? AIJHIP_OK : mhip(le, "KSPSolve iteration");
-    };
-    // the poll batch as a HIP graph: RCCL only (the host transport waits on
-    // the host inside the exchanges); captured on the handle's own stream
-    // and re-captured when what it baked in changes (x, the batch length,
-    // the tolerances and norm, the set-up)
-    const bool use_graph = C->kind == AIJHIP_COMM_RCCL && K->graph == 1;  // (-1: the default, off)
-    static const bool gdbg = std::getenv("AIJHIP_GRAPH_DEBUG") != nullptr;
-    auto dbg = [&](const char *what) {
-        if (gdbg) std::fprintf(stderr, "[kspmpi graph, rank %d] %s\n", C->rank, what);
-    };
-    uint64_t key = 1469598103934665603ULL;
-    for (double v : {p.rtol, p.abstol, p.dtol})
-        key = (key ^ std::hash<double>{}(v)) * 1099511628211ULL;
-    key = (key ^ (uint64_t)(uint32_t)p.max_it ^ ((uint64_t)(uint32_t)p.normtype << 32) ^
-           ((uint64_t)(uint32_t)p.pc << 40)) * 1099511628211ULL;
-    key = (key ^ K->gens[0] ^ (K->gens[1] << 1) ^ (K->gens[2] << 2) ^ (K->gens[3] << 3) ^
-           (uint64_t)(uintptr_t)K->d_state) * 1099511628211ULL;
     K->graph_batches = 0;
-    int32_t launched = 0;
-    for (;;) {
-        if ((e = hipMemcpyAsync(K->h_state, K->d_state, sizeof(CGState), hipMemcpyDeviceToHost, s)) != hipSuccess)
-            return mhip(e, "KSPSolve poll");
-        if ((rc = wait_stream(C, s))) return rc;
-        if (use_graph) dbg("polled");
-        if (K->h_state->done || launched >= K->max_it) break;
-        const int32_t poll = K->poll;  // every CG and V-cycle kernel returns at once past the flag
-        if (use_graph && K->max_it - launched >= poll) {
-            if (!K->gexec || K->g_x != x || K->g_poll != poll || K->g_key != key) {
-                if (K->gexec) (void)hipGraphExecDestroy(K->gexec);
-                K->gexec = nullptr;
-                if (!K->gs && (e = hipStreamCreateWithFlags(&K->gs, hipStreamNonBlocking)) != hipSuccess)
-                    return mhip(e, "KSPSolve capture stream");
-                dbg("begin capture");
-                if ((e = hipStreamBeginCapture(K->gs, hipStreamCaptureModeRelaxed)) != hipSuccess)
-                    return mhip(e, "KSPSolve capture");
-                int crc = AIJHIP_OK;
-                aijhip_mpi::g_capturing = true;
-                for (int j = 0; j < poll && !crc; ++j) {
-                    crc = iteration(K->gs);
-                    dbg("iteration captured");
-                }
-                aijhip_mpi::g_capturing = false;
-                hipGraph_t graph = nullptr;
-                e = hipStreamEndCapture(K->gs, &graph);
-                dbg(e == hipSuccess ? "end capture" : "end capture failed");
-                if (!crc && e == hipSuccess) e = hipGraphInstantiate(&K->gexec, graph, nullptr, nullptr, 0);
-                dbg(e == hipSuccess ? "instantiated" : "instantiate failed");
-                if (graph) (void)hipGraphDestroy(graph);
-                if (crc) return crc;
-                if (e != hipSuccess) {
-                    K->gexec = nullptr;
-                    return mhip(e, "KSPSolve capture (end / instantiate)");
-                }
-                K->g_x = x;
-                K->g_poll = poll;
-                K->g_key = key;
-            }
-            if ((e = hipGraphLaunch(K->gexec, s)) != hipSuccess) return mhip(e, "KSPSolve graph launch");
-            dbg("batch launched");
-            launched += poll;
-            ++K->graph_batches;
-            continue;
-        }
-        for (int j = 0; j < poll && launched < K->max_it; ++j, ++launched)
-            if ((rc = iteration(s))) return rc;
-    }
-    hipLaunchKernelGGL(k_final_x, vg, vt, 0, s, m, K->d_p, x, K->d_state);
-    if ((e = hipGetLastError()) != hipSuccess ||
-        (e = hipMemcpyAsync(K->h_state, K->d_state, sizeof(CGState), hipMemcpyDeviceToHost, s)) != hipSuccess)
-        return mhip(e, "KSPSolve final update");
-    if ((rc = wait_stream(C, s))) return rc;
+    MpiOperator op(K);
+    rc = cg_solve(K->cg, op, b, x, reinterpret_cast<hipStream_t>(stream));
     K->host_syncs = (int32_t)(C->waits - waits0);
-    const CGState &st = *K->h_state;
-    K->its = st.its;
-    K->reason = st.reason ? st.reason : AIJHIP_KSP_DIVERGED_ITS;
-    K->rnorm = st.dp;
-    const int32_t nh = std::min<int32_t>(K->hist_cap, st.its + 1);
-    K->hist.resize((size_t)std::max(nh, 0));
-    if (nh > 0 &&
-        (e = hipMemcpy(K->hist.data(), K->d_hist, sizeof(double) * (size_t)nh, hipMemcpyDeviceToHost)) != hipSuccess)
-        return mhip(e, "residual history");
-    return AIJHIP_OK;
+    return rc;
 }
 
 int aijhip_kspmpi_get_iteration_number(aijhip_kspmpi_t K, int32_t *its) {
     if (!K || !its) return mfail(AIJHIP_ERR_ARG, "NULL argument");
-    *its = K->its;
+    *its = K->cg.its;
     return AIJHIP_OK;
 }
 
 int aijhip_kspmpi_get_residual_norm(aijhip_kspmpi_t K, double *rnorm) {
     if (!K || !rnorm) return mfail(AIJHIP_ERR_ARG, "NULL argument");
-    *rnorm = K->rnorm;
+    *rnorm = K->cg.rnorm;
     return AIJHIP_OK;
 }
 
 int aijhip_kspmpi_get_converged_reason(aijhip_kspmpi_t K, int *reason) {
     if (!K || !reason) return mfail(AIJHIP_ERR_ARG, "NULL argument");
-    *reason = K->reason;
+    *reason = K->cg.reason;
     return AIJHIP_OK;
 }
 
 int aijhip_kspmpi_get_residual_history(aijhip_kspmpi_t K, double *hist, int32_t na, int32_t *n) {
     if (!K || !n || (na > 0 && !hist)) return mfail(AIJHIP_ERR_ARG, "NULL argument");
-    const int32_t c = std::min<int32_t>(na, (int32_t)K->hist.size());
-    std::copy(K->hist.begin(), K->hist.begin() + c, hist);
+    const int32_t c = std::min<int32_t>(na, (int32_t)K->cg.hist.size());
+    std::copy(K->cg.hist.begin(), K->cg.hist.begin() + c, hist);
     *n = c;
     return AIJHIP_OK;
 }
