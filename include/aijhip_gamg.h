@@ -63,6 +63,34 @@ typedef struct aijhip_gamg_host *aijhip_gamg_host_t;
 
 int aijhip_gamg_params_default(aijhip_gamg_params_t *p);
 
+/* The level smoother of the V-cycle (every level but the coarsest, which stays
+ * preonly + Jacobi; the same down and up), after PETSc 3.7's
+ * KSPSolve_Richardson / KSPSolve_Chebyshev with a Jacobi PC [ext]:
+ *   Richardson(its), scale s: x = s D^-1 b from a zero guess, then
+ *     x = x + s D^-1 (b - A x). its = 1, s = 1 is the default.
+ *   Chebyshev(its) on D^-1 A over [emin, emax] = [lo, hi] x the level's
+ *     emax(D^-1 A) estimate (the one the set-up makes to smooth the
+ *     prolongator: it needs nsmooths > 0), PETSc's GAMG default. With
+ *     scale and omega_i from aijhip_mg_cheby_coefficients:
+ *       p_0 = scale D^-1 b (zero guess) or x + scale D^-1 (b - A x),
+ *       p_(i+1) = ((1 - omega_i) p_(i-1) + omega_i p_i)
+ *                 + omega_i scale D^-1 (b - A p_i),  p_(-1) = the guess,
+ *     the result p_its: its products down, its + 1 up. */
+enum { AIJHIP_MG_SMOOTH_RICHARDSON = 0, AIJHIP_MG_SMOOTH_CHEBYSHEV = 1 };
+#define AIJHIP_MG_MAX_ITS 16
+typedef struct aijhip_mg_smoother {
+    int32_t type;             /* -mg_levels_ksp_type (RICHARDSON)             */
+    int32_t its;              /* -mg_levels_ksp_max_it (1), 1..16             */
+    double richardson_scale;  /* -mg_levels_ksp_richardson_scale (1.0)        */
+    double cheby_lo, cheby_hi;/* emin = lo*emax_est, emax = hi*emax_est (0.05, 1.05) */
+} aijhip_mg_smoother_t;
+int aijhip_mg_smoother_default(aijhip_mg_smoother_t *s);
+/* The Chebyshev schedule for its = k steps on [emin, emax], in double:
+ *   scale = 2/(emax+emin); alpha = 1 - scale*emin; mu = 1/alpha;
+ *   c_(-1) = 1, c_0 = mu, c_(i+1) = 2 mu c_i - c_(i-1),
+ *   omega_i = (2/alpha) c_i / c_(i+1)   (omega[0..k)). */
+int aijhip_mg_cheby_coefficients(double emax, double emin, int32_t k, double *scale, double *omega);
+
 /* Build the hierarchy for the square CSR operator (host arrays). Level 0 is
  * the input operator; level l+1 = Pt_l A_l P_l. */
 int aijhip_gamg_build_host(int32_t m, const int32_t *ai, const int32_t *aj, const double *aa,

@@ -30,7 +30,8 @@ typedef struct aijhip_ksp *aijhip_ksp_t;
 
 /* PCType: PCNONE, PCJACOBI (= bjacobi + jacobi sub-PC on one rank,
  * PETSc_SolverOptions_GAMG.info:16-21), PCGAMG (agg, one V-cycle per
- * application: Richardson(1) + Jacobi smoothing down and up on every level,
+ * application: Richardson(1) + Jacobi smoothing down and up on every level
+ * unless aijhip_ksp_set_mg_smoother chose another smoother,
  * preonly + Jacobi on the coarsest — PETSc_SolverOptions_GAMG.info:6-21;
  * hierarchy from include/aijhip_gamg.h). */
 enum {
@@ -105,14 +106,36 @@ int aijhip_ksp_get_host_syncs(aijhip_ksp_t ksp, int32_t *n);
  * passes' reads and writes — CG's p = z + b p (with the deferred x += a p),
  * the r update, and for GAMG per level the Jacobi pass, the residual and
  * post-smoothing SpMVs with their b / D^-1 reads, MatRestrict (P^T),
- * MatInterpolateAdd (P, reading the level's x) and the coarse Jacobi. The
- * per-part split: *spmv_bytes of the total are matrix launches, *level0 of
- * the total belong to the finest level (its SpMVs and vectors). Valid after
- * set-up; the first iteration moves a little less. */
+ * MatInterpolateAdd (P, reading the level's x) and the coarse Jacobi.
+ * With another level smoother (aijhip_ksp_set_mg_smoother) each smoothed
+ * level of m rows adds, with D = 8 (1 where D^-1 is read through a row
+ * template's id) and fused passes:
+ *   Richardson(k): 2 (k - 1) products of A_l, each with (8 + D) m of row
+ *     operands (b, D^-1);
+ *   Chebyshev(k): 2 k products of A_l: down, the first step (8 + D) m (b,
+ *     D^-1) and each later one (16 + D) m (p_(i-1) too); up, the start
+ *     (8 + D) m — the one post-smoothing product the default already counts —
+ *     and each of the k steps (16 + D) m.
+ * Unfused levels (AIJHIP_MG_UNFUSED=1): each added product is followed by a
+ * vector pass of 40 m (Richardson, Chebyshev's start and first step down) or
+ * 48 m (the other Chebyshev steps).
+ * The per-part split: *spmv_bytes of the total are matrix launches, *level0
+ * of the total belong to the finest level (its SpMVs and vectors). Valid
+ * after set-up; the first iteration moves a little less. */
 int aijhip_ksp_get_iteration_bytes(aijhip_ksp_t ksp, int64_t *bytes, int64_t *spmv_bytes, int64_t *level0);
 /* GAMG options (before set-up); NULL = PETSc defaults
  * (aijhip_gamg_params_default). */
 int aijhip_ksp_set_gamg_params(aijhip_ksp_t ksp, const aijhip_gamg_params_t *p);
+/* The GAMG level smoother (aijhip_gamg.h; before set-up, a change clears it);
+ * NULL = the default, Richardson(1) with scale 1. AIJHIP_ERR_ARG with a message
+ * for its outside 1..16, lo <= 0, lo >= hi or an unknown type; Chebyshev with
+ * nsmooths = 0 (no emax estimate) fails at set-up with AIJHIP_ERR_ARG. */
+int aijhip_ksp_set_mg_smoother(aijhip_ksp_t ksp, const aijhip_mg_smoother_t *s);
+/* The smoother of the set-up PC's level `level`: type, its and, for Chebyshev,
+ * the bounds the level uses (lo, hi x its emax estimate; 0, 0 for Richardson).
+ * Any out pointer may be NULL. */
+int aijhip_ksp_get_mg_smoother(aijhip_ksp_t ksp, int32_t level, int32_t *type, int32_t *its, double *emin,
+                               double *emax);
 /* Multigrid levels of the set-up PC (1 for non-GAMG): rows and operator nnz
  * per level (finest first; up to cap entries), and the host set-up time. */
 int aijhip_ksp_get_pc_levels(aijhip_ksp_t ksp, int32_t *nlevels, int32_t *rows, int64_t *nnz,

@@ -157,6 +157,9 @@ int aijhip_kspmpi_create(aijhip_mpiaij_t M, aijhip_kspmpi_t *out);
 int aijhip_kspmpi_set_tolerances(aijhip_kspmpi_t K, double rtol, double abstol, double dtol, int32_t max_it);
 int aijhip_kspmpi_set_pc_type(aijhip_kspmpi_t K, int pc_type);
 int aijhip_kspmpi_set_gamg_params(aijhip_kspmpi_t K, const aijhip_gamg_params_t *p);
+/* The GAMG level smoother, as aijhip_ksp_set_mg_smoother (NULL = default):
+ * of the distributed hierarchy, or of the per-rank one. */
+int aijhip_kspmpi_set_mg_smoother(aijhip_kspmpi_t K, const aijhip_mg_smoother_t *s);
 int aijhip_kspmpi_set_norm_type(aijhip_kspmpi_t K, int norm_type);
 /* Iterations launched between two host polls of the device stop flag
  * (default 8). Every kernel of an iteration is a no-op once the flag is set,

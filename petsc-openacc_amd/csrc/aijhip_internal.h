@@ -338,8 +338,9 @@ hipError_t launch_stream_dot(const aijhip_mat &A, const double *x, double *y, do
                              const int *stop, hipStream_t s);
 // Fused V-cycle smoothing SpMVs on a STREAM plan (same conditions as
 // stream_dot_fusable): the pre-smoothing residual r = b - A x, and one
-// Richardson+Jacobi step x = t + D^-1 (b - A t) (x != t) with optional
-// z.z / z.b partials (2 x n_blocks) for CG on the finest level.
+// Richardson+Jacobi step x = t + D^-1 (b - A t) (x != t) or one Chebyshev step
+// (launch_mg_cheby), with optional z.z / z.b partials (2 x n_blocks) for CG on
+// the finest level.
 bool stream_mg_fusable(const aijhip_mat &A);
 // y = D^-1 A x in PETSc's row order (exact), for the GAMG set-up.
 hipError_t launch_dinv_mult(const aijhip_mat &A, const double *dinv, const double *x, double *y, hipStream_t s);
@@ -348,8 +349,16 @@ hipError_t launch_mult_exact(const aijhip_mat &A, const double *x, double *y, hi
 // r = b - A x on a STREAM plan (residual in the SpMV epilogue).
 hipError_t launch_mg_resid(const aijhip_mat &A, const double *x, const double *b, double *r, hipStream_t s,
                            const int *stop = nullptr);
+// scale: the Richardson scale, x = t + scale D^-1 (b - A t) (1: today's launch).
 hipError_t launch_mg_post(const aijhip_mat &A, const double *t, const double *b, const double *dinv, double *x,
-                          double *dpart, hipStream_t s, const int *stop = nullptr, const double *tdinv = nullptr);
+                          double *dpart, hipStream_t s, const int *stop = nullptr, const double *tdinv = nullptr,
+                          double scale = 1.0);
+// One Chebyshev smoothing step out = (c0 pm1 + c1 pk) + c2 D^-1 (b - A pk) in
+// the SpMV epilogue; pm1 NULL: out = c1 pk + c2 D^-1 (b - A pk) (the first step
+// from a zero guess). out may be pm1, never pk. dpart / tdinv as launch_mg_post.
+hipError_t launch_mg_cheby(const aijhip_mat &A, const double *pm1, const double *pk, const double *b,
+                           const double *dinv, double *out, double c0, double c1, double c2, double *dpart,
+                           hipStream_t s, const int *stop = nullptr, const double *tdinv = nullptr);
 // The kernel, mode and arrays that serve A's STREAM row blocks for `ask`: the
 // one place that decides it (the launchers and mult_layout_bytes read it).
 StreamLayout stream_layout(const aijhip_mat &A, StreamAsk ask);

@@ -179,7 +179,9 @@ struct OpMgResid {
 // must not alias t. With dot, the finest level also yields CG's z.z and z.b
 // partials (z = x, b = CG's residual). TD (row templates): D^-1 of row o is
 // tdinv[pid[o]], the template's (the same bits as dinv[o]).
-template <bool NT, bool TD = false, bool XS = false>
+// SC: the Richardson scale `sc` in place of the literal 1.0 (Richardson with a
+// scale, or Chebyshev's start from a nonzero guess, p_0 = x + scale D^-1 (b - A x)).
+template <bool NT, bool TD = false, bool XS = false, bool SC = false>
 struct OpMgPost {
     static constexpr int kDots = 2;
     static constexpr bool kSeeded = false;
@@ -192,17 +194,19 @@ struct OpMgPost {
     bool dot;
     const uint8_t *pid = nullptr;
     const double *tdinv = nullptr;
+    double sc = 1.0;
     struct Row {
         double to, bo, dio;
     };
     __device__ double di(int o) const { return TD ? tdinv[pid[o]] : dinv[o]; }
+    __device__ double scale() const { return SC ? sc : 1.0; }
     __device__ double gx(int32_t j) const { return t[j]; }
     __device__ double seed(int) const { return 0.0; }
     __device__ Row row(int o) const { return {t[o], b[o], di(o)}; }
     __device__ Row row_td(int o, double td) const { return {XS ? 0.0 : t[o], b[o], td}; }  // td = tdinv[pid[o]]
     __device__ void set_diag(Row &w, double td) const { w.to = td; }
     __device__ void put(int o, double v, double *d, const Row &w) const {
-        const double xo = w.to + 1.0 * (w.dio * (w.bo + (-1.0) * v));
+        const double xo = w.to + scale() * (w.dio * (w.bo + (-1.0) * v));
         if constexpr (NT) st_stream(x + o, xo);
         else x[o] = xo;
         if (dot) {
@@ -212,7 +216,7 @@ struct OpMgPost {
     }
     __device__ void put(int o, double v, double *d) const {
         const double bo = b[o];
-        const double xo = t[o] + 1.0 * (di(o) * (bo + (-1.0) * v));
+        const double xo = t[o] + scale() * (di(o) * (bo + (-1.0) * v));
         if constexpr (NT) st_stream(x + o, xo);
         else x[o] = xo;
         if (dot) {
@@ -220,6 +224,53 @@ struct OpMgPost {
             d[1] += xo * bo;
         }
     }
+};
+
+// One Chebyshev step of a V-cycle smoother on D^-1 A (SpMV of p_k + the
+// elementwise pass, same roundings):
+//   out_i = ((c0 pm1_i + c1 pk_i) + c2 (dinv_i (b_i + (-1) (A pk)_i)))
+// with c0 = 1 - omega, c1 = omega, c2 = omega scale from the host. P0: no
+// p_km1 (the first step from a zero guess): out_i = c1 pk_i + c2 (...). out
+// may be pm1's storage (a row reads only its own pm1[o], in the lane that
+// writes it) and must not be pk's. TD / XS as OpMgPost: D^-1 per template,
+// pk[o] from the row's gathered diagonal slot. With dot, z.z and z.b partials
+// as OpMgPost (the last finest-level post-smoothing step).
+template <bool NT, bool TD = false, bool XS = false, bool P0 = false>
+struct OpMgCheby {
+    static constexpr int kDots = 2;
+    static constexpr bool kSeeded = false;
+    static constexpr bool kTmplDiag = TD;
+    static constexpr bool kXoFromSlot = XS;
+    const double *pm1, *pk, *b, *dinv;
+    double *out;
+    double c0, c1, c2;
+    bool dot;
+    const uint8_t *pid = nullptr;
+    const double *tdinv = nullptr;
+    struct Row {
+        double mo, ko, bo, dio;
+    };
+    __device__ double di(int o) const { return TD ? tdinv[pid[o]] : dinv[o]; }
+    __device__ double gx(int32_t j) const { return pk[j]; }
+    __device__ double seed(int) const { return 0.0; }
+    __device__ Row row(int o) const { return {P0 ? 0.0 : pm1[o], pk[o], b[o], di(o)}; }
+    __device__ Row row_td(int o, double td) const { return {P0 ? 0.0 : pm1[o], XS ? 0.0 : pk[o], b[o], td}; }
+    __device__ void set_diag(Row &w, double kd) const { w.ko = kd; }
+    __device__ double step(const Row &w, double v) const {
+        const double corr = c2 * (w.dio * (w.bo + (-1.0) * v));
+        if constexpr (P0) return c1 * w.ko + corr;
+        else return (c0 * w.mo + c1 * w.ko) + corr;
+    }
+    __device__ void put(int o, double v, double *d, const Row &w) const {
+        const double xo = step(w, v);
+        if constexpr (NT) st_stream(out + o, xo);
+        else out[o] = xo;
+        if (dot) {
+            d[0] += xo * xo;
+            d[1] += xo * w.bo;
+        }
+    }
+    __device__ void put(int o, double v, double *d) const { put(o, v, d, row(o)); }
 };
 
 // y = D^-1 A x (the GAMG set-up's power iteration, gamg_setup.cpp dinv_apply).
@@ -2199,16 +2250,54 @@ hipError_t launch_mg_resid(const aijhip_mat &A, const double *x, const double *b
     return launch_stream_op(A, OpMgResid<true>{x, b, r}, nullptr, s, -1, stop);
 }
 
-hipError_t launch_mg_post(const aijhip_mat &A, const double *t, const double *b, const double *dinv, double *x,
-                          double *dpart, hipStream_t s, const int *stop, const double *tdinv) {
+// (scale == 1: the literal-1.0 instantiations, today's smoother bit for bit)
+template <bool SC>
+static hipError_t launch_mg_post_sc(const aijhip_mat &A, const double *t, const double *b, const double *dinv,
+                                    double *x, double *dpart, hipStream_t s, const int *stop, const double *tdinv,
+                                    double scale) {
+    const bool dot = dpart != nullptr;
     if (tdinv && A.plan.d_pid && A.plan.d_pval) {  // row templates: D^-1 per template
         if (A.plan.tmpl_diag && template_pipelined(A.plan))  // the pipelined launch: t[r] from the diagonal slot
-            return launch_stream_op(A, OpMgPost<true, true, true>{t, b, dinv, x, dpart != nullptr, A.plan.d_pid, tdinv},
+            return launch_stream_op(A, OpMgPost<true, true, true, SC>{t, b, dinv, x, dot, A.plan.d_pid, tdinv, scale},
                                     dpart, s, -1, stop);
-        return launch_stream_op(A, OpMgPost<true, true>{t, b, dinv, x, dpart != nullptr, A.plan.d_pid, tdinv}, dpart,
-                                s, -1, stop);
+        return launch_stream_op(A, OpMgPost<true, true, false, SC>{t, b, dinv, x, dot, A.plan.d_pid, tdinv, scale},
+                                dpart, s, -1, stop);
     }
-    return launch_stream_op(A, OpMgPost<true>{t, b, dinv, x, dpart != nullptr}, dpart, s, -1, stop);
+    return launch_stream_op(A, OpMgPost<true, false, false, SC>{t, b, dinv, x, dot, nullptr, nullptr, scale}, dpart, s,
+                            -1, stop);
+}
+
+hipError_t launch_mg_post(const aijhip_mat &A, const double *t, const double *b, const double *dinv, double *x,
+                          double *dpart, hipStream_t s, const int *stop, const double *tdinv, double scale) {
+    if (t == x) return hipErrorInvalidValue;
+    return scale == 1.0 ? launch_mg_post_sc<false>(A, t, b, dinv, x, dpart, s, stop, tdinv, scale)
+                        : launch_mg_post_sc<true>(A, t, b, dinv, x, dpart, s, stop, tdinv, scale);
+}
+
+template <bool P0>
+static hipError_t launch_mg_cheby_p(const aijhip_mat &A, const double *pm1, const double *pk, const double *b,
+                                    const double *dinv, double *out, double c0, double c1, double c2, double *dpart,
+                                    hipStream_t s, const int *stop, const double *tdinv) {
+    const bool dot = dpart != nullptr;
+    if (tdinv && A.plan.d_pid && A.plan.d_pval) {  // the same choice of TD / XS as launch_mg_post
+        if (A.plan.tmpl_diag && template_pipelined(A.plan))
+            return launch_stream_op(
+                A, OpMgCheby<true, true, true, P0>{pm1, pk, b, dinv, out, c0, c1, c2, dot, A.plan.d_pid, tdinv}, dpart,
+                s, -1, stop);
+        return launch_stream_op(
+            A, OpMgCheby<true, true, false, P0>{pm1, pk, b, dinv, out, c0, c1, c2, dot, A.plan.d_pid, tdinv}, dpart, s,
+            -1, stop);
+    }
+    return launch_stream_op(A, OpMgCheby<true, false, false, P0>{pm1, pk, b, dinv, out, c0, c1, c2, dot}, dpart, s, -1,
+                            stop);
+}
+
+hipError_t launch_mg_cheby(const aijhip_mat &A, const double *pm1, const double *pk, const double *b,
+                           const double *dinv, double *out, double c0, double c1, double c2, double *dpart,
+                           hipStream_t s, const int *stop, const double *tdinv) {
+    if (out == pk) return hipErrorInvalidValue;
+    return pm1 ? launch_mg_cheby_p<false>(A, pm1, pk, b, dinv, out, c0, c1, c2, dpart, s, stop, tdinv)
+               : launch_mg_cheby_p<true>(A, pm1, pk, b, dinv, out, c0, c1, c2, dpart, s, stop, tdinv);
 }
 
 hipError_t launch_dinv_mult(const aijhip_mat &A, const double *dinv, const double *x, double *y, hipStream_t s) {

@@ -39,7 +39,8 @@ struct Hierarchy {
 };
 
 // PCSetUp_GAMG over the distributed operator M0 (p2p halo). Collective.
-int build(aijhip_mpiaij *M0, const aijhip_gamg_params_t &p, Hierarchy &H);
+// sm: the level smoother (its scalars and third vector go into each level's view).
+int build(aijhip_mpiaij *M0, const aijhip_gamg_params_t &p, const aijhip_mg_smoother_t &sm, Hierarchy &H);
 // This rank's rows of level l's operator ('A') or interpolation ('P') on the
 // host, columns in the global numbering of their level (tests).
 int get_level(const Hierarchy &H, int32_t l, char which, int64_t *rstart, int32_t *m, std::vector<int64_t> &ai,

@@ -1213,7 +1213,7 @@ void Hierarchy::destroy() {
         }
         aijhip_mat_destroy(L.Pd);
         aijhip_mat_destroy(L.Po);
-        hipFree(L.dinv); hipFree(L.b); hipFree(L.x); hipFree(L.r);
+        hipFree(L.dinv); hipFree(L.b); hipFree(L.x); hipFree(L.r); hipFree(L.w);
     }
     lv.clear();
     view.clear();
@@ -1301,7 +1301,8 @@ struct PJob {
     }
 };
 
-int build(aijhip_mpiaij *M0, const aijhip_gamg_params_t &p, Hierarchy &H) {
+int build(aijhip_mpiaij *M0, const aijhip_gamg_params_t &p, const aijhip_mg_smoother_t &sm, Hierarchy &H) {
+    if (const int src = aijhip::mg_check_smoother(sm, &p)) return src;
     aijhip::Range range("PCSetUp_GAMG (MPIAIJ)");
     H.destroy();
     aijhip_comm *C = M0->comm;
@@ -2005,6 +2006,13 @@ int build(aijhip_mpiaij *M0, const aijhip_gamg_params_t &p, Hierarchy &H) {
         Level &L = H.lv[l];
         L.op_next = l + 1 < H.lv.size() ? H.lv[l + 1].op : nullptr;
         L.fused = !unfused && aijhip::stream_mg_fusable(*L.Ad);
+        if (l + 1 < H.lv.size()) {  // the smoother's scalars from the level's emax, its third vector
+            rc = aijhip::mg_set_smoother(sm, L.emax, L);
+            if (!rc && aijhip::mg_smoother_needs_w(L) &&
+                (e = hipMalloc(&L.w, sizeof(double) * (size_t)std::max<int32_t>(L.m, 1))) != hipSuccess)
+                rc = gerr(e, "smoother vector");
+            if (rc) break;
+        }
         H.view.push_back(L);
     }
     if (!rc && (e = hipDeviceSynchronize()) != hipSuccess) rc = gerr(e, "set-up");

@@ -52,6 +52,7 @@ struct aijhip_ksp {
     // (Those A/B forms were withdrawn in round 4.)
     CGSolve cg;
     aijhip_gamg_params_t gamg;
+    aijhip_mg_smoother_t smoother;  // of every GAMG level but the coarsest (aijhip_ksp_set_mg_smoother)
     bool set_up = false;
     uint64_t a_gen = 0;  // the operator's plan generation at set-up: a re-planned
                          // operator (options, MatAssemblyEnd) is set up again
@@ -73,7 +74,7 @@ void mg_free(aijhip_ksp *K) {
     for (MGLevel &L : K->mg) {
         if (L.own_A) aijhip_mat_destroy(L.A);
         aijhip_mat_destroy(L.P);
-        hipFree(L.dinv); hipFree(L.b); hipFree(L.x); hipFree(L.r); hipFree(L.tdinv);
+        hipFree(L.dinv); hipFree(L.b); hipFree(L.x); hipFree(L.r); hipFree(L.tdinv); hipFree(L.w);
     }
     K->mg.clear();
     K->mgview.clear();
@@ -137,6 +138,8 @@ struct KspOperator final : CGOperator {
 int gamg_setup(aijhip_ksp *K) {
     aijhip::Range range("PCSetUp_GAMG");
     aijhip_mat *A = K->A;
+    int rc = aijhip::mg_check_smoother(K->smoother, &K->gamg);
+    if (rc) return rc;
     const bool log = std::getenv("AIJHIP_GAMG_LOG") != nullptr;
     auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -149,7 +152,7 @@ int gamg_setup(aijhip_ksp *K) {
     std::vector<aijhip_gamg::DeviceLevel> dl;
     std::vector<double> B;
     bool more = false, overflow = false;
-    int rc = aijhip_gamg::build_device(A, K->gamg, dl, B, &more, &overflow);
+    rc = aijhip_gamg::build_device(A, K->gamg, dl, B, &more, &overflow);
     if (rc) return rc;
     K->setup_path.clear();
     K->setup_cols.clear();
@@ -191,7 +194,11 @@ int gamg_setup(aijhip_ksp *K) {
         K->setup_cols.push_back(-1);
     }
     K->mg.assign((size_t)nl, MGLevel());
+    std::vector<double> lambda((size_t)nl, 0.0);  // each level's emax(D^-1 A) estimate (none on the coarsest)
+    for (int32_t hl = 0; hl + 1 < nh; ++hl)
+        aijhip_gamg_host_level_info(H, hl, nullptr, nullptr, nullptr, &lambda[nd - 1 + hl]);
     for (int32_t l = 0; l < nd; ++l) {  // the device levels move into the KSP
+        if (dl[l].P) lambda[l] = dl[l].emax;
         K->mg[l].A = dl[l].A;
         K->mg[l].own_A = l > 0;
         K->mg[l].P = dl[l].P;
@@ -244,6 +251,13 @@ int gamg_setup(aijhip_ksp *K) {
         if (!L.P->transpose && (rc = aijhip_mat_mult_transpose(L.P, L.r, K->mg[l + 1].b, nullptr))) return rc;
     }
     for (MGLevel &L : K->mg) L.fused = !std::getenv("AIJHIP_MG_UNFUSED") && aijhip::stream_mg_fusable(*L.A);
+    for (int32_t l = 0; l + 1 < nl; ++l) {  // the smoother's scalars, and its third vector where it rotates one
+        MGLevel &L = K->mg[l];
+        if ((rc = aijhip::mg_set_smoother(K->smoother, lambda[l], L))) return rc;
+        if (aijhip::mg_smoother_needs_w(L) &&
+            (e = hipMalloc(&L.w, sizeof(double) * (size_t)std::max<int32_t>(L.m, 1))) != hipSuccess)
+            return cg_hip(e, "GAMG: smoother vector");
+    }
     if (K->mg[0].fused &&
         (e = hipMalloc(&K->d_mgpart, sizeof(double) * 2 * (size_t)std::max(1, K->mg[0].A->plan.n_blocks))) !=
             hipSuccess)
@@ -271,6 +285,7 @@ int aijhip_ksp_create(aijhip_mat_t A, aijhip_ksp_t *out) {
     if (!K) return cg_fail(AIJHIP_ERR_ALLOC, "host allocation");
     K->A = A;
     aijhip_gamg_params_default(&K->gamg);
+    aijhip_mg_smoother_default(&K->smoother);
     *out = K;
     return AIJHIP_OK;
 }
@@ -299,6 +314,31 @@ int aijhip_ksp_set_gamg_params(aijhip_ksp_t K, const aijhip_gamg_params_t *p) {
     if (p) K->gamg = *p;
     else aijhip_gamg_params_default(&K->gamg);
     if (K->cg.pc == AIJHIP_PC_GAMG) K->set_up = false;
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_set_mg_smoother(aijhip_ksp_t K, const aijhip_mg_smoother_t *sm) {
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    aijhip_mg_smoother_t v;
+    aijhip_mg_smoother_default(&v);
+    if (sm) v = *sm;
+    const int rc = aijhip::mg_check_smoother(v);
+    if (rc) return rc;
+    K->smoother = v;
+    if (K->cg.pc == AIJHIP_PC_GAMG) K->set_up = false;
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_get_mg_smoother(aijhip_ksp_t K, int32_t l, int32_t *type, int32_t *its, double *emin, double *emax) {
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    if (!K->set_up || K->cg.pc != AIJHIP_PC_GAMG) return cg_fail(AIJHIP_ERR_STATE, "GAMG not set up");
+    if (l < 0 || l + 1 >= (int32_t)K->mg.size())
+        return cg_fail(AIJHIP_ERR_ARG, "no such smoothed level (the coarsest is preonly + Jacobi)");
+    const MGLevel &L = K->mg[l];
+    if (type) *type = L.smooth;
+    if (its) *its = L.its;
+    if (emin) *emin = L.cmin;
+    if (emax) *emax = L.cmax;
     return AIJHIP_OK;
 }
 
@@ -412,6 +452,17 @@ int aijhip_ksp_get_iteration_bytes(aijhip_ksp_t K, int64_t *bytes, int64_t *spmv
                     sp = la + lt + lp + la, v = 24 * ml + 8 * ml + 8 * ml + 16 * ml;
                 else  // the same with the residual and Richardson passes separate
                     sp = la + lt + lp + la, v = 24 * ml + 24 * ml + 8 * ml + 40 * ml;
+                // another smoother's added products and their row operands
+                // (include/aijhip_ksp.h lists them; D: D^-1 or a template id)
+                const int64_t k = L.its, D = L.fused && L.tdinv ? 1 : 8;
+                if (L.smooth == AIJHIP_MG_SMOOTH_CHEBYSHEV) {
+                    sp += 2 * k * la;
+                    v += L.fused ? ((8 + D) + (k - 1) * (16 + D) + k * (16 + D)) * ml
+                                 : (40 + (k - 1) * 48 + k * 48) * ml;
+                } else {
+                    sp += 2 * (k - 1) * la;
+                    v += 2 * (k - 1) * (L.fused ? 8 + D : 40) * ml;
+                }
             }
             spmv += sp;
             vec += v;

@@ -690,6 +690,8 @@ struct aijhip_kspmpi {
     double setup_seconds = 0.0;
     aijhip_gamg_params_t gamg{};
     bool gamg_set = false;
+    aijhip_mg_smoother_t smoother{};  // the GAMG level smoother (aijhip_kspmpi_set_mg_smoother)
+    bool smoother_set = false;
     double *d_opart = nullptr;  // A_o's p.w correction partials (k_offdiag)
     // The poll batch (poll iterations) captured once into a HIP graph and
     // replayed by one hipGraphLaunch (aijhip_kspmpi_set_graph): the RCCL
@@ -754,12 +756,16 @@ int kspmpi_set_up(aijhip_kspmpi *K) {
         if (K->gamg_set) gp = K->gamg;
         else aijhip_gamg_params_default(&gp);
         K->dh = new (std::nothrow) aijhip_gamg_mpi::Hierarchy();
-        rc = K->dh ? aijhip_gamg_mpi::build(M, gp, *K->dh) : mfail(AIJHIP_ERR_ALLOC, "host allocation");
+        aijhip_mg_smoother_t sm;
+        aijhip_mg_smoother_default(&sm);
+        if (K->smoother_set) sm = K->smoother;
+        rc = K->dh ? aijhip_gamg_mpi::build(M, gp, sm, *K->dh) : mfail(AIJHIP_ERR_ALLOC, "host allocation");
     } else if (!rc && (pc == AIJHIP_PC_GAMG || pc == AIJHIP_PC_BJACOBI_GAMG)) {
         // PCSetUp_BJacobi + the sub-PC's PCSetUp_GAMG on A_d (at one rank: PCGAMG itself)
         rc = aijhip_ksp_create(A, &K->sub);
         if (!rc) rc = aijhip_ksp_set_pc_type(K->sub, AIJHIP_PC_GAMG);
         if (!rc && K->gamg_set) rc = aijhip_ksp_set_gamg_params(K->sub, &K->gamg);
+        if (!rc && K->smoother_set) rc = aijhip_ksp_set_mg_smoother(K->sub, &K->smoother);
         if (!rc) rc = aijhip_ksp_set_up(K->sub);
     }
     if (rc) {
@@ -1153,6 +1159,18 @@ int aijhip_kspmpi_set_gamg_params(aijhip_kspmpi_t K, const aijhip_gamg_params_t 
     K->gamg_set = p != nullptr;
     if (p) K->gamg = *p;
     if (K->cg.pc == AIJHIP_PC_GAMG) K->set_up = false;
+    return AIJHIP_OK;
+}
+
+int aijhip_kspmpi_set_mg_smoother(aijhip_kspmpi_t K, const aijhip_mg_smoother_t *sm) {
+    if (!K) return mfail(AIJHIP_ERR_ARG, "NULL ksp");
+    if (sm) {
+        const int rc = aijhip::mg_check_smoother(*sm);
+        if (rc) return rc;
+        K->smoother = *sm;
+    }
+    K->smoother_set = sm != nullptr;
+    if (K->cg.pc == AIJHIP_PC_GAMG || K->cg.pc == AIJHIP_PC_BJACOBI_GAMG) K->set_up = false;
     return AIJHIP_OK;
 }
 

@@ -9,6 +9,9 @@
 //            [-pc_gamg_threshold T] [-pc_gamg_agg_nsmooths S]
 //            [-pc_gamg_coarse_eq_limit C] [-pc_mg_levels L] [-pc_gamg_square_graph G]
 //            [-aijhip_gamg_coarsen 1|0] [-aijhip_gamg_eig_ksp 1|0] [-aijhip_host_assembly]
+//            [-aijhip_mg_levels_ksp_type richardson|chebyshev] [-aijhip_mg_levels_ksp_max_it K]
+//            [-aijhip_mg_levels_ksp_richardson_scale S] [-aijhip_mg_levels_esteig LO,HI]
+//            [-aijhip_iteration_bytes]
 //
 // Options come from the command line and from a PETSc options file
 // (`-key value` per line, '#' comments; PetscOptionsInsertFile,
@@ -107,6 +110,8 @@ int main(int argc, char **argv) {
     }
     aijhip_gamg_params_t gp;
     aijhip_gamg_params_default(&gp);
+    aijhip_mg_smoother_t sm;
+    aijhip_mg_smoother_default(&sm);
     if (pc == AIJHIP_PC_GAMG) {
         // PETSc_SolverOptions_GAMG.info:6-21. The level smoother and coarse
         // solver are fixed to that file's choice (Richardson(1) + Jacobi,
@@ -129,6 +134,33 @@ int main(int argc, char **argv) {
         // power-iteration emax of rounds 1-4 (PETSc has no such switch)
         gp.coarsen = (int32_t)geti("-aijhip_gamg_coarsen", gp.coarsen);
         gp.eig_ksp = (int32_t)geti("-aijhip_gamg_eig_ksp", gp.eig_ksp);
+        // the level smoother under this build's own names (the PETSc-named
+        // -mg_levels_* options above stay refused): checked here, before any
+        // device is opened
+        const std::string st = gets("-aijhip_mg_levels_ksp_type", "richardson");
+        if (st != "richardson" && st != "chebyshev") {
+            std::fprintf(stderr, "main_ksp: -aijhip_mg_levels_ksp_type %s not supported (richardson or chebyshev)\n",
+                         st.c_str());
+            return 1;
+        }
+        sm.type = st == "chebyshev" ? AIJHIP_MG_SMOOTH_CHEBYSHEV : AIJHIP_MG_SMOOTH_RICHARDSON;
+        sm.its = (int32_t)geti("-aijhip_mg_levels_ksp_max_it", sm.its);
+        if (sm.its < 1 || sm.its > AIJHIP_MG_MAX_ITS) {
+            std::fprintf(stderr, "main_ksp: -aijhip_mg_levels_ksp_max_it %d not supported (1..%d)\n", sm.its,
+                         AIJHIP_MG_MAX_ITS);
+            return 1;
+        }
+        sm.richardson_scale = getd("-aijhip_mg_levels_ksp_richardson_scale", sm.richardson_scale);
+        if (opt.count("-aijhip_mg_levels_esteig")) {
+            const std::string &v = opt["-aijhip_mg_levels_esteig"];
+            char tail = 0;
+            if (std::sscanf(v.c_str(), "%lf,%lf%c", &sm.cheby_lo, &sm.cheby_hi, &tail) != 2 || !(sm.cheby_lo > 0.0) ||
+                !(sm.cheby_lo < sm.cheby_hi)) {
+                std::fprintf(stderr, "main_ksp: -aijhip_mg_levels_esteig %s not supported (lo,hi with 0 < lo < hi)\n",
+                             v.c_str());
+                return 1;
+            }
+        }
     }
     const std::string nts = gets("-ksp_norm_type", "preconditioned");
     const int normtype = nts == "unpreconditioned" ? AIJHIP_KSP_NORM_UNPRECONDITIONED
@@ -178,6 +210,7 @@ int main(int argc, char **argv) {
                                   getd("-ksp_divtol", 1e5), (int32_t)geti("-ksp_max_it", 10000)));
     CHK(aijhip_ksp_set_pc_type(ksp, pc));
     if (pc == AIJHIP_PC_GAMG) CHK(aijhip_ksp_set_gamg_params(ksp, &gp));
+    if (pc == AIJHIP_PC_GAMG) CHK(aijhip_ksp_set_mg_smoother(ksp, &sm));
     CHK(aijhip_ksp_set_norm_type(ksp, normtype));
     CHK(aijhip_ksp_set_up(ksp));
     HCHK(hipDeviceSynchronize());
@@ -208,6 +241,12 @@ int main(int argc, char **argv) {
                 "L2 norm of final residual: %f\n" "Maximum norm of error: %f\n"
                 "Time [init, create solver, solve]: [%f, %f, %f]\n",
                 nx, ny, nz, its, res, linf, t_sys - t_start, t_solver - t_sys, t_solve - t_solver);
+    if (opt.count("-aijhip_iteration_bytes")) {  // aijhip_ksp_get_iteration_bytes, for the roofline
+        int64_t nb = 0, nb_spmv = 0, nb_l0 = 0;
+        CHK(aijhip_ksp_get_iteration_bytes(ksp, &nb, &nb_spmv, &nb_l0));
+        std::printf("Bytes per iteration [all, SpMV, finest level]: [%lld, %lld, %lld]\n", (long long)nb,
+                    (long long)nb_spmv, (long long)nb_l0);
+    }
     std::fflush(stdout);
 
     CHK(aijhip_ksp_destroy(ksp));

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "aijhip_gamg.h"
 #include "aijhip_internal.h"
 
 struct aijhip_mpiaij;
@@ -27,7 +28,26 @@ struct MGLevelView {
     double *tdinv = nullptr;  // row templates: D^-1 per template (else NULL)
     double *b = nullptr, *x = nullptr, *r = nullptr;  // level 0: b and x are the caller's
     bool fused = false;  // smoothing passes fused into STREAM launches (AIJHIP_MG_UNFUSED=1: PETSc's order)
+    // The level smoother (mg_set_smoother; the coarsest level ignores it):
+    // Richardson(its) with rscale, or Chebyshev(its) on D^-1 A over
+    // [cmin, cmax] with the host's scale and omega[0..its)
+    int32_t smooth = AIJHIP_MG_SMOOTH_RICHARDSON, its = 1;
+    double rscale = 1.0;
+    double cmin = 0.0, cmax = 0.0, scale = 0.0, omega[AIJHIP_MG_MAX_ITS] = {};
+    double *w = nullptr;  // one more level vector where the smoother rotates three (mg_smoother_needs_w)
 };
+
+// A smoother request checked (its in 1..AIJHIP_MG_MAX_ITS, 0 < lo < hi, a known
+// type) and, at set-up (p != NULL), against the hierarchy's parameters:
+// Chebyshev needs each level's emax(D^-1 A) estimate, which the set-up makes
+// only to smooth the prolongator (nsmooths > 0). AIJHIP_ERR_ARG with a message.
+int mg_check_smoother(const aijhip_mg_smoother_t &s, const aijhip_gamg_params_t *p = nullptr);
+// Fills L's smoother fields from the request and the level's emax(D^-1 A)
+// estimate lambda (Chebyshev: bounds lo * lambda, hi * lambda and the
+// coefficient schedule of aijhip_mg_cheby_coefficients).
+int mg_set_smoother(const aijhip_mg_smoother_t &s, double lambda, MGLevelView &L);
+// Whether a smoothed level with L's smoother and `fused` needs L.w.
+bool mg_smoother_needs_w(const MGLevelView &L);
 
 // PCApply_MG (multiplicative, one V-cycle): x0 = B b0 on `s`. Every kernel
 // takes CG's stop flag (NULL outside a solve) and returns at once past it;

@@ -1,20 +1,36 @@
 // mg_cycle.hip — PCApply_MG, one multiplicative V-cycle (mg_cycle.h).
 //
-// Smoother: KSPSolve_Richardson with one iteration, scale 1, Jacobi PC [ext]:
-//   zero guess:     x = 0 + 1.0 * (D^-1 b)           = D^-1 b
-//   nonzero guess:  x = x + 1.0 * (D^-1 (b + (-1) A x))
+// Level smoothers (the same down and up), after KSPSolve_Richardson /
+// KSPSolve_Chebyshev with a Jacobi PC [ext]; nothing is contracted to an FMA
+// and every sum is added left to right as written:
+//   Richardson(k), scale s (default k = 1, s = 1):
+//     zero guess:     x = s (D^-1 b)           (s = 1: x = D^-1 b)
+//     every other:    x = x + s (D^-1 (b + (-1) A x))
+//   Chebyshev(k) with the host's scale and omega_i (mg_set_smoother):
+//     zero guess:     p_km1 = 0;  p_k = scale (D^-1 b)
+//     nonzero guess:  p_km1 = x;  p_k = x + scale (D^-1 (b + (-1) A x))
+//     step i:         p_kp1 = ((1 - omega_i) p_km1 + omega_i p_k)
+//                             + (omega_i scale) (D^-1 (b + (-1) A p_k))
+//     (from a zero guess step 0 has no p_km1 term); x = p_k after k steps.
 // Coarsest level: preonly + Jacobi. On STREAM-planned levels the smoothing
-// passes ride in the SpMV (aijhip::launch_mg_resid / _post): the residual
-// rides in the SpMV after the x = D^-1 b vector pass, and interpolation
-// writes t = x + P x_c to the level's scratch so the post-smoothing launch
-// reads t and writes x. Across ranks those launches run over A_d while the
-// halo moves, then A_o's share is added on the boundary rows.
+// passes ride in the SpMV (aijhip::launch_mg_resid / _post / _cheby): the
+// zero-guess start is a vector pass, the residual rides in the SpMV after it,
+// and interpolation writes t = x + P x_c where the post-smoothing launches
+// read it. The steps rotate two of the level's vectors — x and w going down
+// (the residual takes r), x and r coming up; a Chebyshev step writes p_kp1 over
+// p_km1 — from a first buffer chosen by the parity of the step count, so the
+// result lands in x (level 0: the caller's vector) without a copy. Unfused
+// levels run MatMult into r and an elementwise pass with the same expression
+// (Richardson in place, Chebyshev rotating x and w). Across ranks the fused
+// launches run over A_d while the halo moves, then A_o's share is added on
+// the boundary rows.
 //
 // Every halo_post is followed by exactly one halo_finish or halo_abort on
 // every return path (mpi_internal.h).
 #include "mg_cycle.h"
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 
 #include "mpi_internal.h"
@@ -26,20 +42,24 @@ using aijhip_mpi::halo_abort;
 using aijhip_mpi::halo_finish;
 using aijhip_mpi::halo_post;
 
-// The vector passes. Elementwise, so the grid does not change a bit.
+// The vector passes. Elementwise, so the grid does not change a bit. SC: the
+// factor f (Richardson's scale, Chebyshev's scale) in place of the literal 1.
+template <bool SC>
 __global__ __launch_bounds__(kVecThreads) void k_jacobi(int64_t n, const double *__restrict__ dinv,
-                                                        const double *__restrict__ b, double *x,
+                                                        const double *__restrict__ b, double *x, double f,
                                                         const int *stop) {
     if (stop && *stop) return;
-    GRID_STRIDE(i, n) x[i] = dinv[i] * b[i];
+    GRID_STRIDE(i, n) x[i] = SC ? f * (dinv[i] * b[i]) : dinv[i] * b[i];
 }
 
 // The same on row templates: D^-1 of row i is tdinv[pid[i]] (the same bits)
+template <bool SC>
 __global__ __launch_bounds__(kVecThreads) void k_jacobi_t(int64_t n, const uint8_t *__restrict__ pid,
                                                           const double *__restrict__ tdinv,
-                                                          const double *__restrict__ b, double *x, const int *stop) {
+                                                          const double *__restrict__ b, double *x, double f,
+                                                          const int *stop) {
     if (stop && *stop) return;
-    GRID_STRIDE(i, n) x[i] = tdinv[pid[i]] * b[i];
+    GRID_STRIDE(i, n) x[i] = SC ? f * (tdinv[pid[i]] * b[i]) : tdinv[pid[i]] * b[i];
 }
 
 // MatResidual: r = b + (-1) r, where r holds A x on entry (VecAYPX(r,-1,b)).
@@ -49,27 +69,44 @@ __global__ __launch_bounds__(kVecThreads) void k_resid(int64_t n, const double *
     GRID_STRIDE(i, n) r[i] = b[i] + (-1.0) * r[i];
 }
 
+// y = x + f (D^-1 (b - A x)) with ax = A x; y may be x
+template <bool SC>
 __global__ __launch_bounds__(kVecThreads) void k_richardson(int64_t n, const double *__restrict__ dinv,
                                                             const double *__restrict__ b,
-                                                            const double *__restrict__ ax, double *x,
-                                                            const int *stop) {
+                                                            const double *__restrict__ ax, const double *x, double *y,
+                                                            double f, const int *stop) {
     if (stop && *stop) return;
-    GRID_STRIDE(i, n) x[i] = x[i] + 1.0 * (dinv[i] * (b[i] + (-1.0) * ax[i]));
+    GRID_STRIDE(i, n) y[i] = x[i] + (SC ? f : 1.0) * (dinv[i] * (b[i] + (-1.0) * ax[i]));
 }
 
-// y[o] = y[o] + scale[o] * (-(A_o g)_o) over A_o's rows (scale NULL: 1): the
-// off-diagonal block's share of a fused residual (r = b - A_d x - A_o g) or
-// post-smoothing (x = t + D^-1 (b - A_d t - A_o g)) on the boundary rows
+// One Chebyshev step with ax = A p_k (OpMgCheby's expression); out may be pm1
+template <bool P0>
+__global__ __launch_bounds__(kVecThreads) void k_cheby_step(int64_t n, const double *__restrict__ dinv,
+                                                            const double *__restrict__ b,
+                                                            const double *__restrict__ ax, const double *pm1,
+                                                            const double *__restrict__ pk, double *out, double c0,
+                                                            double c1, double c2, const int *stop) {
+    if (stop && *stop) return;
+    GRID_STRIDE(i, n) {
+        const double corr = c2 * (dinv[i] * (b[i] + (-1.0) * ax[i]));
+        out[i] = P0 ? c1 * pk[i] + corr : (c0 * pm1[i] + c1 * pk[i]) + corr;
+    }
+}
+
+// y[o] = y[o] + (f scale[o]) * (-(A_o g)_o) over A_o's rows (scale NULL: 1):
+// the off-diagonal block's share of a fused residual (r = b - A_d x - A_o g)
+// or smoothing step (x = t + f D^-1 (b - A_d t - A_o g)) on the boundary rows
 __global__ __launch_bounds__(256) void k_offdiag_axpy(int32_t nr, const int32_t *__restrict__ rai,
                                                       const int32_t *__restrict__ ridx, const int32_t *__restrict__ aj,
                                                       const double *__restrict__ aa, const double *__restrict__ g,
-                                                      const double *__restrict__ scale, double *y, const int *stop) {
+                                                      const double *__restrict__ scale, double f, double *y,
+                                                      const int *stop) {
     if (stop && *stop) return;
     for (int32_t q = blockIdx.x * 256 + threadIdx.x; q < nr; q += gridDim.x * 256) {
         const int32_t o = ridx ? ridx[q] : q;
         double sum = 0.0;
         for (int32_t k = rai[q]; k < rai[q + 1]; ++k) sum += aa[k] * g[aj[k]];
-        y[o] = y[o] + (scale ? scale[o] : 1.0) * (-sum);
+        y[o] = y[o] + (scale ? f * scale[o] : 1.0) * (-sum);
     }
 }
 
@@ -123,19 +160,87 @@ int restrict_to(const MGLevelView &L, const double *r, double *b, hipStream_t s,
 }
 
 // The A_o correction of a fused smoothing launch (after the halo landed).
-int offdiag_axpy(const MGLevelView &L, const double *scale, double *y, hipStream_t s, const int *stop) {
+int offdiag_axpy(const MGLevelView &L, const double *scale, double f, double *y, hipStream_t s, const int *stop) {
     if (!L.Ao) return AIJHIP_OK;
     const aijhip::RowList R = aijhip::row_list(*L.Ao);
     if (R.nr == 0) return AIJHIP_OK;
     hipLaunchKernelGGL(k_offdiag_axpy, dim3((unsigned)((R.nr + 255) / 256)), dim3(256), 0, s, R.nr, R.rai, R.ridx,
-                       L.Ao->d_aj, L.Ao->d_aa, L.op->d_ghost, scale, y, stop);
+                       L.Ao->d_aj, L.Ao->d_aa, L.op->d_ghost, scale, f, y, stop);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? AIJHIP_OK : gerr(e, "off-diagonal smoothing share");
 }
 
+int sfail(const char *msg) {
+    aijhip::set_error(std::string("MG smoother: ") + msg);
+    return AIJHIP_ERR_ARG;
+}
+
 }  // namespace
 
+extern "C" {
+
+int aijhip_mg_smoother_default(aijhip_mg_smoother_t *s) {
+    if (!s) return sfail("NULL argument");
+    s->type = AIJHIP_MG_SMOOTH_RICHARDSON;
+    s->its = 1;
+    s->richardson_scale = 1.0;
+    s->cheby_lo = 0.05;
+    s->cheby_hi = 1.05;
+    return AIJHIP_OK;
+}
+
+int aijhip_mg_cheby_coefficients(double emax, double emin, int32_t k, double *scale, double *omega) {
+    if (!scale || !omega) return sfail("NULL argument");
+    if (k < 1 || k > AIJHIP_MG_MAX_ITS) return sfail("its must be in 1..16");
+    if (!(emin > 0.0) || !(emax > emin)) return sfail("Chebyshev needs 0 < emin < emax");
+    *scale = 2.0 / (emax + emin);
+    const double alpha = 1.0 - *scale * emin;
+    const double mu = 1.0 / alpha, omegaprod = 2.0 / alpha;
+    double c_km1 = 1.0, c_k = mu;
+    for (int32_t i = 0; i < k; ++i) {
+        const double c_kp1 = 2.0 * mu * c_k - c_km1;
+        omega[i] = omegaprod * c_k / c_kp1;
+        c_km1 = c_k;
+        c_k = c_kp1;
+    }
+    return AIJHIP_OK;
+}
+
+}  // extern "C"
+
 namespace aijhip {
+
+int mg_check_smoother(const aijhip_mg_smoother_t &s, const aijhip_gamg_params_t *p) {
+    if (s.type != AIJHIP_MG_SMOOTH_RICHARDSON && s.type != AIJHIP_MG_SMOOTH_CHEBYSHEV)
+        return sfail("unknown type (richardson or chebyshev)");
+    if (s.its < 1 || s.its > AIJHIP_MG_MAX_ITS) return sfail("its must be in 1..16");
+    if (!(s.cheby_lo > 0.0)) return sfail("Chebyshev bounds: lo must be positive");
+    if (!(s.cheby_lo < s.cheby_hi)) return sfail("Chebyshev bounds: lo must be below hi");
+    if (!std::isfinite(s.richardson_scale) || !std::isfinite(s.cheby_hi))
+        return sfail("the Richardson scale and the Chebyshev bounds must be finite");
+    if (p && s.type == AIJHIP_MG_SMOOTH_CHEBYSHEV && p->nsmooths <= 0)
+        return sfail("Chebyshev needs each level's emax(D^-1 A) estimate, which the set-up makes only to smooth the "
+                     "prolongator: nsmooths = 0 leaves none");
+    return AIJHIP_OK;
+}
+
+int mg_set_smoother(const aijhip_mg_smoother_t &s, double lambda, MGLevelView &L) {
+    const int rc = mg_check_smoother(s);
+    if (rc) return rc;
+    L.smooth = s.type;
+    L.its = s.its;
+    L.rscale = s.richardson_scale;
+    L.cmin = L.cmax = L.scale = 0.0;
+    if (s.type != AIJHIP_MG_SMOOTH_CHEBYSHEV) return AIJHIP_OK;
+    if (!(lambda > 0.0)) return sfail("Chebyshev: the level has no emax(D^-1 A) estimate");
+    L.cmin = s.cheby_lo * lambda;
+    L.cmax = s.cheby_hi * lambda;
+    return aijhip_mg_cheby_coefficients(L.cmax, L.cmin, L.its, &L.scale, L.omega);
+}
+
+bool mg_smoother_needs_w(const MGLevelView &L) {
+    return L.smooth == AIJHIP_MG_SMOOTH_CHEBYSHEV || (L.fused && L.its > 1);
+}
 
 int mg_vcycle(const std::vector<MGLevelView> &lv, const double *b0, double *x0, hipStream_t s, const int *stop,
               double *dots, bool *dots_done) {
@@ -150,22 +255,85 @@ int mg_vcycle(const std::vector<MGLevelView> &lv, const double *b0, double *x0, 
     const dim3 t(kVecThreads);
     int rc;
     hipError_t e;
+    // x = f (D^-1 b): the zero-guess start of either smoother, the coarse solve (f = 1)
+    auto jacobi = [&](const MGLevelView &L, int l, double f, double *x) {
+        const dim3 g = grid(L);
+        const int64_t m = L.m;
+        if (L.fused && L.tdinv && l < nl - 1) {
+            const uint8_t *pid = L.Ad->plan.d_pid;
+            if (f == 1.0) hipLaunchKernelGGL(k_jacobi_t<false>, g, t, 0, s, m, pid, L.tdinv, B(l), x, f, stop);
+            else hipLaunchKernelGGL(k_jacobi_t<true>, g, t, 0, s, m, pid, L.tdinv, B(l), x, f, stop);
+        } else if (f == 1.0) {
+            hipLaunchKernelGGL(k_jacobi<false>, g, t, 0, s, m, L.dinv, B(l), x, f, stop);
+        } else {
+            hipLaunchKernelGGL(k_jacobi<true>, g, t, 0, s, m, L.dinv, B(l), x, f, stop);
+        }
+    };
+    // One smoothing step from pk with one product of A. cheby: out = (c0 pm1
+    // + c1 pk) + c2 D^-1 (b - A pk) (pm1 NULL: no c0 term), out may be pm1;
+    // else Richardson: out = pk + c2 D^-1 (b - A pk). Fused: out != pk, the
+    // launch over A_d while the halo moves and A_o's share after; unfused:
+    // MatMult into r, then the elementwise pass. dp: CG's z.z / z.b partials.
+    auto step = [&](const MGLevelView &L, int l, bool cheby, const double *pm1, const double *pk, double *out,
+                    double c0, double c1, double c2, double *dp) -> int {
+        if (!L.fused) {
+            int rc1 = mult(L, pk, L.r, s, stop);
+            if (rc1) return rc1;
+            const dim3 g = grid(L);
+            const int64_t m = L.m;
+            if (!cheby && c2 == 1.0)
+                hipLaunchKernelGGL(k_richardson<false>, g, t, 0, s, m, L.dinv, B(l), L.r, pk, out, c2, stop);
+            else if (!cheby)
+                hipLaunchKernelGGL(k_richardson<true>, g, t, 0, s, m, L.dinv, B(l), L.r, pk, out, c2, stop);
+            else if (!pm1)
+                hipLaunchKernelGGL(k_cheby_step<true>, g, t, 0, s, m, L.dinv, B(l), L.r, pm1, pk, out, c0, c1, c2,
+                                   stop);
+            else
+                hipLaunchKernelGGL(k_cheby_step<false>, g, t, 0, s, m, L.dinv, B(l), L.r, pm1, pk, out, c0, c1, c2,
+                                   stop);
+            return AIJHIP_OK;
+        }
+        const bool ex = exchanges(L.op);
+        int rc1;
+        if (ex && (rc1 = halo_post(L.op, pk, s))) return rc1;
+        const hipError_t e1 =
+            cheby ? launch_mg_cheby(*L.Ad, pm1, pk, B(l), L.dinv, out, c0, c1, c2, dp, s, stop, L.tdinv)
+                  : launch_mg_post(*L.Ad, pk, B(l), L.dinv, out, dp, s, stop, L.tdinv, c2);
+        if (e1 != hipSuccess) return ex ? halo_abort(L.op, s, gerr(e1, "smoothing")) : gerr(e1, "smoothing");
+        if (ex && (rc1 = halo_finish(L.op, s))) return rc1;
+        return offdiag_axpy(L, L.dinv, c2, out, s, stop);
+    };
     for (int l = 0; l < nl; ++l) {
         const MGLevelView &L = lv[l];
+        if (l == nl - 1) {  // coarse: preonly + Jacobi, x = D^-1 b
+            jacobi(L, l, 1.0, X(l));
+            break;
+        }
+        // smoothd from a zero guess: the start, then n steps rotating two
+        // buffers (unfused Richardson: in place) so that the last lands in x
+        const bool cheby = L.smooth == AIJHIP_MG_SMOOTH_CHEBYSHEV;
+        const int n = cheby ? L.its : L.its - 1;
+        const bool inplace = !cheby && !L.fused;
+        if (n > 0 && !inplace && !L.w) return gerr(hipErrorInvalidValue, "no smoother work vector");
+        double *cur = inplace || n % 2 == 0 ? X(l) : L.w, *oth = inplace ? X(l) : n % 2 == 0 ? L.w : X(l);
+        jacobi(L, l, cheby ? L.scale : L.rscale, cur);
+        for (int i = 0; i < n; ++i) {
+            if (cheby)
+                rc = step(L, l, true, i == 0 ? nullptr : oth, cur, oth, 1.0 - L.omega[i], L.omega[i],
+                          L.omega[i] * L.scale, nullptr);
+            else
+                rc = step(L, l, false, nullptr, cur, oth, 0.0, 0.0, L.rscale, nullptr);
+            if (rc) return rc;
+            std::swap(cur, oth);
+        }
         const dim3 g = grid(L);
-        // smoothd (coarse: preonly + Jacobi): x = D^-1 b
-        if (L.fused && L.tdinv && l < nl - 1)
-            hipLaunchKernelGGL(k_jacobi_t, g, t, 0, s, (int64_t)L.m, L.Ad->plan.d_pid, L.tdinv, B(l), X(l), stop);
-        else
-            hipLaunchKernelGGL(k_jacobi, g, t, 0, s, (int64_t)L.m, L.dinv, B(l), X(l), stop);
-        if (l == nl - 1) break;
         if (L.fused) {  // r = b - A x in the SpMV epilogue (over A_d while the halo moves)
             const bool ex = exchanges(L.op);
             if (ex && (rc = halo_post(L.op, X(l), s))) return rc;
             if ((e = launch_mg_resid(*L.Ad, X(l), B(l), L.r, s, stop)) != hipSuccess)
                 return ex ? halo_abort(L.op, s, gerr(e, "residual")) : gerr(e, "residual");
             if (ex && (rc = halo_finish(L.op, s))) return rc;
-            if ((rc = offdiag_axpy(L, nullptr, L.r, s, stop))) return rc;
+            if ((rc = offdiag_axpy(L, nullptr, 1.0, L.r, s, stop))) return rc;
         } else {  // MatMult, then the residual
             if ((rc = mult(L, X(l), L.r, s, stop))) return rc;
             hipLaunchKernelGGL(k_resid, g, t, 0, s, (int64_t)L.m, B(l), L.r, stop);
@@ -175,24 +343,33 @@ int mg_vcycle(const std::vector<MGLevelView> &lv, const double *b0, double *x0, 
     }
     for (int l = nl - 2; l >= 0; --l) {
         const MGLevelView &L = lv[l];
-        if (L.fused) {
-            // MatInterpolateAdd into the scratch: t = x + P x_c, then smoothu
-            // x = t + D^-1 (b - A t) in the SpMV epilogue
-            if ((rc = transfer(L, X(l + 1), X(l), L.r, s, stop))) return rc;
-            double *dp = (l == 0 && dots && !L.Ao) ? dots : nullptr;
-            const bool ex = exchanges(L.op);
-            if (ex && (rc = halo_post(L.op, L.r, s))) return rc;
-            if ((e = launch_mg_post(*L.Ad, L.r, B(l), L.dinv, X(l), dp, s, stop, L.tdinv)) != hipSuccess)
-                return ex ? halo_abort(L.op, s, gerr(e, "post-smoothing")) : gerr(e, "post-smoothing");
-            if (ex && (rc = halo_finish(L.op, s))) return rc;
-            if ((rc = offdiag_axpy(L, L.dinv, X(l), s, stop))) return rc;
-            if (dp && dots_done) *dots_done = true;
-        } else {
-            // MatInterpolateAdd: x = x + P x_c; smoothu: x = x + D^-1 (b - A x)
-            if ((rc = transfer(L, X(l + 1), X(l), X(l), s, stop))) return rc;
-            if ((rc = mult(L, X(l), L.r, s, stop))) return rc;
-            hipLaunchKernelGGL(k_richardson, grid(L), t, 0, s, (int64_t)L.m, L.dinv, B(l), L.r, X(l), stop);
+        // MatInterpolateAdd t = x + P x_c, then smoothu from t: n steps (the
+        // Chebyshev start x + scale D^-1 (b - A x) is a Richardson step).
+        // Fused: t goes to the scratch r or stays in x, by n's parity, the
+        // steps rotate x and r; unfused: r takes the products, Richardson runs
+        // in place (PETSc's order) and Chebyshev rotates x and w.
+        const bool cheby = L.smooth == AIJHIP_MG_SMOOTH_CHEBYSHEV;
+        const int n = cheby ? L.its + 1 : L.its;
+        const bool inplace = !cheby && !L.fused;
+        double *alt = L.fused ? L.r : L.w;
+        if (!inplace && !alt) return gerr(hipErrorInvalidValue, "no smoother work vector");
+        double *cur = inplace || n % 2 == 0 ? X(l) : alt, *oth = inplace ? X(l) : n % 2 == 0 ? alt : X(l);
+        if ((rc = transfer(L, X(l + 1), X(l), cur, s, stop))) return rc;
+        double *dp = (l == 0 && L.fused && dots && !L.Ao) ? dots : nullptr;
+        for (int i = 0; i < n; ++i) {
+            double *dpi = i == n - 1 ? dp : nullptr;
+            if (!cheby) {
+                rc = step(L, l, false, nullptr, cur, oth, 0.0, 0.0, L.rscale, dpi);
+            } else if (i == 0) {
+                rc = step(L, l, false, nullptr, cur, oth, 0.0, 0.0, L.scale, dpi);
+            } else {  // p_kp1 over p_km1 (cur holds p_k, oth p_km1)
+                const double om = L.omega[i - 1];
+                rc = step(L, l, true, oth, cur, oth, 1.0 - om, om, om * L.scale, dpi);
+            }
+            if (rc) return rc;
+            std::swap(cur, oth);
         }
+        if (dp && dots_done) *dots_done = true;
     }
     e = hipGetLastError();
     return e == hipSuccess ? AIJHIP_OK : gerr(e, "kernel launch");

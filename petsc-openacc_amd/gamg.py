@@ -13,7 +13,9 @@ GAMG_SYMBOLS = (
     "aijhip_gamg_params_default", "aijhip_gamg_build_host", "aijhip_gamg_host_num_levels",
     "aijhip_gamg_host_level_info", "aijhip_gamg_host_get_A", "aijhip_gamg_host_get_P",
     "aijhip_gamg_host_get_aggregates", "aijhip_gamg_host_view", "aijhip_gamg_host_destroy",
+    "aijhip_mg_smoother_default", "aijhip_mg_cheby_coefficients",
 )
+SMOOTHER_TYPES = {"richardson": 0, "chebyshev": 1}
 
 
 class GamgParams(ctypes.Structure):
@@ -22,6 +24,12 @@ class GamgParams(ctypes.Structure):
                 ("smooth_scale", ctypes.c_double), ("eig_its", ctypes.c_int32), ("threads", ctypes.c_int32),
                 ("device_min_rows", ctypes.c_int32), ("coarsen", ctypes.c_int32), ("square_graph", ctypes.c_int32),
                 ("eig_ksp", ctypes.c_int32), ("pad0", ctypes.c_int32)]
+
+
+class MgSmoother(ctypes.Structure):
+    """aijhip_mg_smoother_t: the V-cycle's level smoother."""
+    _fields_ = [("type", ctypes.c_int32), ("its", ctypes.c_int32), ("richardson_scale", ctypes.c_double),
+                ("cheby_lo", ctypes.c_double), ("cheby_hi", ctypes.c_double)]
 
 
 _P = ctypes.c_void_p
@@ -44,6 +52,9 @@ def _lib():
         L.aijhip_gamg_host_get_P.argtypes = [_P, ctypes.c_int32, _P, _P, _P]
         L.aijhip_gamg_host_get_aggregates.argtypes = [_P, ctypes.c_int32, _P]
         L.aijhip_gamg_host_destroy.argtypes = [_P]
+        L.aijhip_mg_smoother_default.argtypes = [ctypes.POINTER(MgSmoother)]
+        L.aijhip_mg_cheby_coefficients.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_int32,
+                                                   ctypes.POINTER(ctypes.c_double), _P]
         _bound = True
     return L
 
@@ -54,6 +65,30 @@ def default_params(**over) -> GamgParams:
     for k, v in over.items():
         setattr(p, k, v)
     return p
+
+
+def mg_smoother(type="richardson", its=None, scale=None, lo=None, hi=None) -> MgSmoother:
+    """aijhip_mg_smoother_default with the given fields replaced: type
+    "richardson" or "chebyshev", its = steps per sweep, scale = Richardson's
+    scale, lo / hi = Chebyshev's bounds as factors of the level's emax
+    estimate."""
+    s = MgSmoother()
+    _pkg._check(_lib().aijhip_mg_smoother_default(ctypes.byref(s)))
+    if type not in SMOOTHER_TYPES:
+        raise ValueError(f"smoother type {type!r}: one of {sorted(SMOOTHER_TYPES)}")
+    s.type = SMOOTHER_TYPES[type]
+    for field, v in (("its", its), ("richardson_scale", scale), ("cheby_lo", lo), ("cheby_hi", hi)):
+        if v is not None:
+            setattr(s, field, v)
+    return s
+
+
+def cheby_coefficients(emax: float, emin: float, k: int):
+    """(scale, omega[0..k)) of aijhip_mg_cheby_coefficients."""
+    scale = ctypes.c_double()
+    omega = np.zeros(max(int(k), 1), np.float64)
+    _pkg._check(_lib().aijhip_mg_cheby_coefficients(emax, emin, int(k), ctypes.byref(scale), omega.ctypes.data))
+    return scale.value, omega[: int(k)]
 
 
 def build_host(ai, aj, aa, **params):

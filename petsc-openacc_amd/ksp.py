@@ -29,7 +29,7 @@ KSP_SYMBOLS = (
     "aijhip_ksp_get_residual_history", "aijhip_ksp_get_fused", "aijhip_ksp_destroy",
     "aijhip_ksp_set_gamg_params", "aijhip_ksp_get_pc_levels", "aijhip_ksp_get_pc_level",
     "aijhip_ksp_get_gamg_setup_path", "aijhip_ksp_get_host_syncs", "aijhip_ksp_get_iteration_bytes",
-    "aijhip_ksp_solve_host",
+    "aijhip_ksp_solve_host", "aijhip_ksp_set_mg_smoother", "aijhip_ksp_get_mg_smoother",
 )
 _P = ctypes.c_void_p
 _bound = False
@@ -59,6 +59,10 @@ def _lib():
                                                      ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
         L.aijhip_ksp_destroy.argtypes = [_P]
         L.aijhip_ksp_set_gamg_params.argtypes = [_P, _P]
+        L.aijhip_ksp_set_mg_smoother.argtypes = [_P, _P]
+        L.aijhip_ksp_get_mg_smoother.argtypes = [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double),
+                                                 ctypes.POINTER(ctypes.c_double)]
         L.aijhip_ksp_get_pc_level.argtypes = [_P, ctypes.c_int32, ctypes.c_char, ctypes.POINTER(ctypes.c_int32),
                                               ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64), _P, _P, _P]
         L.aijhip_ksp_get_pc_levels.argtypes = [_P, ctypes.POINTER(ctypes.c_int32), _P, _P, ctypes.c_int32,
@@ -72,7 +76,10 @@ class KSPCG:
     """KSPCG on a SeqAIJHIP operator (device vectors)."""
 
     def __init__(self, A, rtol=1e-5, atol=1e-50, dtol=1e5, max_it=10000, pc="jacobi",
-                 norm="preconditioned", guess_nonzero=False, gamg=None):
+                 norm="preconditioned", guess_nonzero=False, gamg=None, smoother=None):
+        """gamg: aijhip_gamg_params_t fields; smoother: the GAMG level smoother,
+        dict(type="richardson"|"chebyshev", its=, scale=, lo=, hi=) (gamg.mg_smoother;
+        None: Richardson(1), scale 1)."""
         L = _lib()
         self.A = A
         self._h = _P()
@@ -83,6 +90,10 @@ class KSPCG:
             G = importlib.import_module("petsc-openacc_amd.gamg")
             self._gp = G.default_params(**gamg)
             _pkg._check(L.aijhip_ksp_set_gamg_params(self._h, ctypes.byref(self._gp)))
+        if smoother:
+            G = importlib.import_module("petsc-openacc_amd.gamg")
+            self._sm = G.mg_smoother(**smoother)
+            _pkg._check(L.aijhip_ksp_set_mg_smoother(self._h, ctypes.byref(self._sm)))
         _pkg._check(L.aijhip_ksp_set_norm_type(self._h, NORM_TYPES[norm]))
         _pkg._check(L.aijhip_ksp_set_initial_guess_nonzero(self._h, int(guess_nonzero)))
 
@@ -152,6 +163,14 @@ class KSPCG:
         _pkg._check(_lib().aijhip_ksp_get_pc_levels(self._h, ctypes.byref(n), rows.ctypes.data, nnz.ctypes.data,
                                                      32, ctypes.byref(secs)))
         return rows[: n.value].tolist(), nnz[: n.value].tolist(), secs.value
+
+    def mg_smoother(self, level: int):
+        """(type, its, emin, emax) of the set-up PC's smoother on `level`: the
+        bounds are the ones a Chebyshev level uses (0, 0 for Richardson)."""
+        ty, its, lo, hi = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double(), ctypes.c_double()
+        _pkg._check(_lib().aijhip_ksp_get_mg_smoother(self._h, int(level), ctypes.byref(ty), ctypes.byref(its),
+                                                       ctypes.byref(lo), ctypes.byref(hi)))
+        return ("richardson", "chebyshev")[ty.value], its.value, lo.value, hi.value
 
     def setup_path(self):
         """Per coarsening l -> l+1: ("device"|"host", widest product
@@ -230,19 +249,20 @@ def bench_cg(pkg, A, nx, ny, nz, dev, iters=200):
                                  "passes, per iteration, over the measured wall time of the iterations"}}
 
 
-def bench_cg_gamg(pkg, A, nx, ny, nz, dev, rtol=1e-14, atol=1e-12, max_it=10000, gamg=None, light=False):
+def bench_cg_gamg(pkg, A, nx, ny, nz, dev, rtol=1e-14, atol=1e-12, max_it=10000, gamg=None, light=False,
+                  smoother=None):
     """The reference's solver configuration (CG + GAMG to atol 1e-12 / rtol
     1e-14, configs/cg_gamg.info) solved to convergence on the benchmark
     operand from x = 0: KSPSetUp (host hierarchy + uploads) and KSPSolve
     timed separately, the solve once warm (a second solve on the same
     hierarchy, as a time-stepping caller would). gamg: the hierarchy's
     parameters (aijhip_gamg_params_t fields); light: skip the host-vector
-    solve and the second set-up."""
+    solve and the second set-up; smoother: the level smoother (KSPCG's)."""
     import torch
     rhs, exact = pkg.poisson_vectors(nx, ny, nz)
     b = torch.from_numpy(rhs).to(dev)
     x = torch.zeros_like(b)
-    with KSPCG(A, rtol=rtol, atol=atol, max_it=max_it, pc="gamg", gamg=gamg) as ksp:
+    with KSPCG(A, rtol=rtol, atol=atol, max_it=max_it, pc="gamg", gamg=gamg, smoother=smoother) as ksp:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         ksp.set_up()
@@ -281,7 +301,7 @@ def bench_cg_gamg(pkg, A, nx, ny, nz, dev, rtol=1e-14, atol=1e-12, max_it=10000,
     # the same set-up again in this process (a caller that rebuilds the
     # hierarchy after new values): the first one above also pays one-time
     # costs (the set-up kernels' first launch, pinned staging)
-    with KSPCG(A, rtol=rtol, atol=atol, max_it=max_it, pc="gamg", gamg=gamg) as ksp2:
+    with KSPCG(A, rtol=rtol, atol=atol, max_it=max_it, pc="gamg", gamg=gamg, smoother=smoother) as ksp2:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         ksp2.set_up()
@@ -303,8 +323,10 @@ def bench_cg_gamg(pkg, A, nx, ny, nz, dev, rtol=1e-14, atol=1e-12, max_it=10000,
             "time_to_solution_s": round(t_setup + t_solve, 3),
             "levels": [{"rows": r, "nnz": z} for r, z in zip(rows, nnz)],
             "roofline": roof,
-            "options": "cg, gamg agg nsmooths 1 threshold 0, mg levels richardson(1)+jacobi, "
-                       "coarse preonly+jacobi, rtol 1e-14 atol 1e-12"}
+            "options": "cg, gamg agg nsmooths 1 threshold 0, mg levels "
+                       + ("richardson(1)" if not smoother else
+                          f"{smoother.get('type', 'richardson')}({smoother.get('its', 1)})")
+                       + "+jacobi, coarse preonly+jacobi, rtol 1e-14 atol 1e-12"}
 
 
 # ----------------------------------------------------------------------------
