@@ -113,6 +113,53 @@ int aijhip_gamg_host_view(aijhip_gamg_host_t h, int32_t l, char which, const int
                           const double **aa);
 int aijhip_gamg_host_destroy(aijhip_gamg_host_t h);
 
+/* ---- Diagnostics ----
+ * The device set-up's sparse products and prolongator parts on host operands:
+ * each call uploads its arguments, runs the set-up's own device routine
+ * unchanged on the current device and keeps the result on the host, in a
+ * handle read with the getters below (CSR results) or in the caller's arrays.
+ * Operands are CSR with int32 offsets; a B row holds every column at most
+ * once (the products' precondition, not checked), an A row may repeat one. */
+typedef struct aijhip_gamg_diag *aijhip_gamg_diag_t;
+
+/* C = A B, A m x k, B k x n, by the hash-table product the Galerkin operators
+ * are built with. n_cu: the compute-unit count the product sizes its grid and
+ * its tables by (0 = the device's own). AIJHIP_ERR_STATE when a row of C has
+ * more distinct columns than the largest table holds (the set-up then builds
+ * the level on the host); *out is NULL then. */
+int aijhip_gamg_diag_rowprod(int32_t m, int32_t k, int32_t n, const int32_t *ai, const int32_t *aj,
+                             const double *aa, const int32_t *bi, const int32_t *bj, const double *ba,
+                             int32_t n_cu, aijhip_gamg_diag_t *out);
+/* T = A P0, A m x k, P0 k x na with one entry per row: column agg[j], value
+ * p0[j], none where agg[j] = -1 (the product the prolongator is smoothed
+ * with: its register form, or the hash-table product when a row has more
+ * than 8 distinct columns or A more than 8 entries per row). */
+int aijhip_gamg_diag_rowprod_p0(int32_t m, int32_t k, int32_t na, const int32_t *ai, const int32_t *aj,
+                                const double *aa, const int32_t *agg, const double *p0, int32_t n_cu,
+                                aijhip_gamg_diag_t *out);
+/* P = P0 + alpha D^-1 T on the union pattern: T m x n with ascending columns,
+ * P0's row i the entry (agg[i], p0[i]) or none (agg[i] = -1), dinv[i] = 1/d_i. */
+int aijhip_gamg_diag_prolong(int32_t m, int32_t n, const int32_t *ti, const int32_t *tj, const double *ta,
+                             const int32_t *agg, const double *p0, const double *dinv, double alpha,
+                             aijhip_gamg_diag_t *out);
+/* The tentative prolongator of the near-null space B[0, m) over aggregates
+ * agg[i] in [-1, na): s2[a] = the sum of B_i^2 over a's members in ascending
+ * i, Bc[a] = its square root, p0[i] = B[i] / Bc[agg[i]] (0 where Bc is 0 or
+ * agg[i] = -1). b_ones != 0: B is all 1.0 (the finest level's form). */
+int aijhip_gamg_diag_tentative(int32_t m, int32_t na, const int32_t *agg, const double *B, int32_t b_ones,
+                               double *Bc, double *p0, double *s2);
+/* The result's rows, columns and entries; the hash-table launches recorded
+ * (npasses); whether the register form of A P0 wrote the result. */
+int aijhip_gamg_diag_info(aijhip_gamg_diag_t h, int32_t *m, int32_t *n, int64_t *nz, int32_t *npasses,
+                          int32_t *p0_register);
+int aijhip_gamg_diag_get_csr(aijhip_gamg_diag_t h, int32_t *ai, int32_t *aj, double *aa);
+/* passes[4 p .. 4 p + 3] = lanes per row, table slots, mode (0 count, 1
+ * write) and the most keys a row may hold in the table (keys_max) of launch
+ * p, in launch order; row_table[i] = the slots of the table that wrote row i
+ * (0: not a hash-table product). Either may be NULL. */
+int aijhip_gamg_diag_get_passes(aijhip_gamg_diag_t h, int32_t *passes, int32_t *row_table);
+int aijhip_gamg_diag_destroy(aijhip_gamg_diag_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -350,3 +350,79 @@ def vcycle(levels, b):
         return x
 
     return cycle(0, np.asarray(b, dtype=np.float64))
+
+
+# ---------------------------------------------------------------------------
+# The device set-up's sparse products and prolongator parts, restated one row
+# at a time (tests/test_gamg_products*.py compare the device routines with
+# these bit for bit). CSR operands are (ai, aj, aa) tuples; nothing here is
+# fused: every product is rounded before it is added.
+
+def rowprod_ref(A, B):
+    """C = A B in traversal order: for row i, A's entries in storage order,
+    for each B row k's entries in storage order, p = a_ik * b_kj (rounded)
+    added to column j's sum, which starts from 0.0. Columns ascending; every
+    column reached is stored, a sum of 0.0 included."""
+    ai, aj, aa = (np.asarray(x) for x in A)
+    bi, bj, ba = (np.asarray(x) for x in B)
+    ci, cj, ca = [0], [], []
+    for i in range(len(ai) - 1):
+        ks = aj[ai[i]:ai[i + 1]]
+        if len(ks):
+            lens = bi[ks + 1] - bi[ks]
+            # positions of B's entries, B row after B row, in storage order
+            pos = np.repeat(bi[ks] - np.concatenate(([0], np.cumsum(lens)[:-1])), lens) + np.arange(lens.sum())
+            prods = np.repeat(aa[ai[i]:ai[i + 1]], lens) * ba[pos]
+            cols, inv = np.unique(bj[pos], return_inverse=True)
+            sums = np.zeros(len(cols))
+            np.add.at(sums, inv, prods)  # unbuffered: one add after the other, in traversal order
+            cj.append(cols)
+            ca.append(sums)
+        ci.append(ci[-1] + (len(cj[-1]) if len(ks) else 0))
+    return (np.asarray(ci, np.int32), np.concatenate(cj).astype(np.int32) if cj else np.zeros(0, np.int32),
+            np.concatenate(ca) if ca else np.zeros(0))
+
+
+def p0_csr_ref(agg, p0):
+    """The tentative prolongator as a CSR: row j holds (agg[j], p0[j]), or
+    nothing where agg[j] = -1."""
+    agg = np.asarray(agg)
+    member = agg >= 0
+    ai = np.concatenate(([0], np.cumsum(member))).astype(np.int32)
+    return ai, agg[member].astype(np.int32), np.asarray(p0, np.float64)[member]
+
+
+def prolong_ref(T, agg, p0, dinv, alpha):
+    """P = P0 + alpha D^-1 T on the union pattern: alpha * (dinv[i] * t) +
+    (p0[i] if c == agg[i] else 0.0) for T's entries, p0[i] alone where T's
+    row lacks column agg[i] (gamg_setup.cpp prolongator)."""
+    ti, tj, ta = (np.asarray(x) for x in T)
+    pi, pj, pa = [0], [], []
+    for i in range(len(ti) - 1):
+        g = int(agg[i])
+        row = {int(c): alpha * (dinv[i] * t) + (p0[i] if int(c) == g else 0.0)
+               for c, t in zip(tj[ti[i]:ti[i + 1]], ta[ti[i]:ti[i + 1]])}
+        if g >= 0 and g not in row:
+            row[g] = p0[i]
+        for c in sorted(row):
+            pj.append(c)
+            pa.append(row[c])
+        pi.append(len(pj))
+    return np.asarray(pi, np.int32), np.asarray(pj, np.int32), np.asarray(pa, np.float64)
+
+
+def tentative_ref(agg, B, na):
+    """(Bc, p0, s2): s2[a] = the sum of B_i^2 over a's members in ascending i
+    from 0.0, Bc = sqrt(s2), p0[i] = B[i] / Bc[agg[i]], 0 where Bc is 0 or
+    agg[i] = -1."""
+    agg = np.asarray(agg)
+    B = np.asarray(B, np.float64)
+    s2 = np.zeros(na)
+    member = agg >= 0
+    np.add.at(s2, agg[member], (B * B)[member])  # unbuffered: ascending i
+    Bc = np.sqrt(s2)
+    p0 = np.zeros(len(agg))
+    for i in np.flatnonzero(member):
+        if Bc[agg[i]] > 0.0:
+            p0[i] = B[i] / Bc[agg[i]]
+    return Bc, p0, s2

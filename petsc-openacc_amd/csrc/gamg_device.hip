@@ -896,6 +896,18 @@ constexpr int kHashClasses = 6;
 constexpr int kHashT[kHashClasses] = {16, 32, 64, 128, 256, 1024};
 constexpr int kHashClassId = 16;  // klass ids kHashClassId + t
 
+// What a product launched, recorded for the diagnostics (aijhip_gamg_diag_*)
+// while g_trace is set; the launches are the same either way.
+struct ProductTrace {
+    struct Pass {
+        int32_t lanes, table, write, keys_max;
+    };
+    std::vector<Pass> passes;        // every k_rowprod_hash launch, in order
+    std::vector<int32_t> row_table;  // per row of C: the table that wrote it
+    bool p0_register = false;        // k_rowprod_p0 wrote the product
+};
+thread_local ProductTrace *g_trace = nullptr;
+
 template <int G, int T>
 constexpr int hash_groups() {
     return std::max(64 / G, std::min(256 / G, 65536 / (16 * T)));
@@ -911,6 +923,7 @@ hipError_t rowprod_hash_pass(const DCsr &A, const DCsr &B, int32_t *cnt, int32_t
     const int keys_max = A.m < 64 * n_cu ? T / 2 : T - 1;
     constexpr int NG = hash_groups<G, T>();
     static_assert(NG * T * 16 <= 65536, "LDS per workgroup");
+    if (g_trace) g_trace->passes.push_back({G, T, numeric ? 1 : 0, keys_max});
     const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(A.m, NG), (int64_t)n_cu * 32);
     if (!numeric)
         hipLaunchKernelGGL((k_rowprod_hash<G, T, NG, false>), dim3(grid), dim3(G * NG), 0, nullptr, A.m, A.ai, A.aj,
@@ -1010,6 +1023,7 @@ int rowprod_p0(const DCsr &A, const DCsr &P0, const int32_t *agg, const double *
         return herr(e, "numeric product");
     }
     if (cols_used) *cols_used = std::max(*cols_used, kP0Cap);
+    if (g_trace) g_trace->p0_register = true;
     return AIJHIP_OK;
 }
 
@@ -1087,6 +1101,13 @@ int rowprod(const DCsr &A, const DCsr &B, DCsr &C, int n_cu, int *cols_used) {
         for (int t = first; t <= last && e == hipSuccess; ++t)
             e = rowprod_hash_class(t, hash_lanes(G, t), A, B, cnt, klass, false, C.ai, &C, true, n_cu);
         if (e != hipSuccess) return bail(e, "numeric product");
+        if (g_trace) {
+            g_trace->row_table.resize((size_t)A.m);
+            if ((e = hipMemcpy(g_trace->row_table.data(), klass, sizeof(int32_t) * (size_t)A.m,
+                               hipMemcpyDeviceToHost)) != hipSuccess)
+                return bail(e, "product classes");
+            for (int32_t &k : g_trace->row_table) k = kHashT[k - kHashClassId];
+        }
         hipFree(cnt);
         hipFree(klass);
         if (cols_used) *cols_used = std::max(*cols_used, kHashT[last]);
@@ -2174,3 +2195,266 @@ int build_device(aijhip_mat *A0, const aijhip_gamg_params_t &p, std::vector<Devi
 }
 
 }  // namespace aijhip_gamg
+
+// ------------------------------------------------------------ diagnostics
+// include/aijhip_gamg.h "Diagnostics": the device products and prolongator
+// parts on host operands, through the routines above unchanged.
+
+struct aijhip_gamg_diag {
+    int32_t m = 0, n = 0;
+    std::vector<int32_t> ai, aj;
+    std::vector<double> aa;
+    ProductTrace trace;
+};
+
+namespace {
+
+int dfail(int code, const char *what) {
+    set_error(std::string("GAMG diagnostics: ") + what);
+    return code;
+}
+
+// host CSR (m rows, columns in [0, ncols)) well formed
+bool host_csr_ok(int32_t m, int64_t ncols, const int32_t *ai, const int32_t *aj, const double *aa) {
+    if (m < 0 || ncols < 0 || !ai || ai[0] != 0) return false;
+    for (int32_t i = 0; i < m; ++i)
+        if (ai[i + 1] < ai[i]) return false;
+    const int32_t nz = ai[m];
+    if (nz > 0 && (!aj || !aa)) return false;
+    for (int32_t k = 0; k < nz; ++k)
+        if (aj[k] < 0 || aj[k] >= ncols) return false;
+    return true;
+}
+
+template <class T>
+hipError_t upload(T **d, const T *h, int64_t count, int64_t pad = 0) {
+    hipError_t e = dalloc(d, count + pad);
+    if (e == hipSuccess && pad > 0) e = hipMemset(*d + count, 0, sizeof(T) * (size_t)pad);
+    if (e == hipSuccess && count > 0) e = hipMemcpy(*d, h, sizeof(T) * (size_t)count, hipMemcpyHostToDevice);
+    return e;
+}
+
+// a device copy of a host CSR (aj / aa with the handles' tail pad)
+hipError_t upload_csr(int32_t m, int32_t n, const int32_t *ai, const int32_t *aj, const double *aa, DCsr &D) {
+    D = DCsr();
+    D.m = m;
+    D.n = n;
+    D.nz = ai[m];
+    hipError_t e;
+    if ((e = upload(&D.ai, ai, (int64_t)m + 1)) != hipSuccess || (e = upload(&D.aj, aj, D.nz, 2)) != hipSuccess ||
+        (e = upload(&D.aa, aa, D.nz, 2)) != hipSuccess)
+        D.release();
+    return e;
+}
+
+// the result's arrays into a new handle (C stays the caller's to release)
+int download_csr(const DCsr &C, aijhip_gamg_diag *h) {
+    h->m = C.m;
+    h->n = C.n;
+    h->ai.resize((size_t)C.m + 1);
+    h->aj.resize((size_t)C.nz);
+    h->aa.resize((size_t)C.nz);
+    hipError_t e = hipMemcpy(h->ai.data(), C.ai, sizeof(int32_t) * ((size_t)C.m + 1), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && C.nz > 0)
+        e = hipMemcpy(h->aj.data(), C.aj, sizeof(int32_t) * (size_t)C.nz, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && C.nz > 0)
+        e = hipMemcpy(h->aa.data(), C.aa, sizeof(double) * (size_t)C.nz, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? AIJHIP_OK : herr(e, "read the result");
+}
+
+int diag_device(int32_t *n_cu) {
+    if (aijhip::visible_devices() <= 0) {
+        set_error(aijhip::no_device_reason());
+        return AIJHIP_ERR_NODEVICE;
+    }
+    if (*n_cu < 0) return dfail(AIJHIP_ERR_ARG, "n_cu < 0");
+    if (*n_cu == 0) {
+        int dev = 0, cus = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess) return herr(e, "device attributes");
+        *n_cu = cus;
+    }
+    return AIJHIP_OK;
+}
+
+struct TraceScope {
+    explicit TraceScope(ProductTrace *t) { g_trace = t; }
+    ~TraceScope() { g_trace = nullptr; }
+};
+
+}  // namespace
+
+extern "C" {
+
+int aijhip_gamg_diag_rowprod(int32_t m, int32_t k, int32_t n, const int32_t *ai, const int32_t *aj, const double *aa,
+                             const int32_t *bi, const int32_t *bj, const double *ba, int32_t n_cu,
+                             aijhip_gamg_diag_t *out) {
+    if (!out) return dfail(AIJHIP_ERR_ARG, "NULL out");
+    *out = nullptr;
+    if (!host_csr_ok(m, k, ai, aj, aa) || !host_csr_ok(k, n, bi, bj, ba)) return dfail(AIJHIP_ERR_ARG, "malformed CSR");
+    int rc = diag_device(&n_cu);
+    if (rc) return rc;
+    DCsr A, B, C;
+    hipError_t e;
+    if ((e = upload_csr(m, k, ai, aj, aa, A)) != hipSuccess || (e = upload_csr(k, n, bi, bj, ba, B)) != hipSuccess) {
+        A.release();
+        return herr(e, "upload");
+    }
+    std::unique_ptr<aijhip_gamg_diag> h(new aijhip_gamg_diag());
+    {
+        TraceScope ts(&h->trace);
+        rc = aijhip_gamg::rowprod_device(A, B, C, n_cu, nullptr);
+    }
+    if (rc == AIJHIP_ERR_STATE) dfail(rc, "a product row has more distinct columns than the largest table holds");
+    if (!rc) rc = download_csr(C, h.get());
+    A.release();
+    B.release();
+    C.release();
+    if (rc) return rc;
+    *out = h.release();
+    return AIJHIP_OK;
+}
+
+int aijhip_gamg_diag_rowprod_p0(int32_t m, int32_t k, int32_t na, const int32_t *ai, const int32_t *aj,
+                                const double *aa, const int32_t *agg, const double *p0, int32_t n_cu,
+                                aijhip_gamg_diag_t *out) {
+    if (!out) return dfail(AIJHIP_ERR_ARG, "NULL out");
+    *out = nullptr;
+    if (!host_csr_ok(m, k, ai, aj, aa) || na < 0 || (k > 0 && (!agg || !p0))) return dfail(AIJHIP_ERR_ARG, "malformed CSR");
+    for (int32_t j = 0; j < k; ++j)
+        if (agg[j] < -1 || agg[j] >= na) return dfail(AIJHIP_ERR_ARG, "aggregate out of range");
+    int rc = diag_device(&n_cu);
+    if (rc) return rc;
+    DCsr A, P0, C;
+    int32_t *d_agg = nullptr;
+    double *d_p0 = nullptr;
+    bool own = false;
+    hipError_t e;
+    if ((e = upload_csr(m, k, ai, aj, aa, A)) != hipSuccess || (e = upload(&d_agg, agg, k)) != hipSuccess ||
+        (e = upload(&d_p0, p0, k)) != hipSuccess || (e = p0_csr(k, na, d_agg, d_p0, P0, &own)) != hipSuccess)
+        rc = herr(e, "upload");
+    std::unique_ptr<aijhip_gamg_diag> h(new aijhip_gamg_diag());
+    if (!rc) {
+        TraceScope ts(&h->trace);
+        rc = rowprod_p0(A, P0, d_agg, d_p0, C, n_cu, nullptr);
+    }
+    if (rc == AIJHIP_ERR_STATE) dfail(rc, "a product row has more distinct columns than the largest table holds");
+    if (!rc) rc = download_csr(C, h.get());
+    hipFree(P0.ai);
+    if (own) {
+        hipFree(P0.aj);
+        hipFree(P0.aa);
+    }
+    hipFree(d_agg);
+    hipFree(d_p0);
+    A.release();
+    C.release();
+    if (rc) return rc;
+    *out = h.release();
+    return AIJHIP_OK;
+}
+
+int aijhip_gamg_diag_prolong(int32_t m, int32_t n, const int32_t *ti, const int32_t *tj, const double *ta,
+                             const int32_t *agg, const double *p0, const double *dinv, double alpha,
+                             aijhip_gamg_diag_t *out) {
+    if (!out) return dfail(AIJHIP_ERR_ARG, "NULL out");
+    *out = nullptr;
+    if (!host_csr_ok(m, n, ti, tj, ta) || (m > 0 && (!agg || !p0 || !dinv))) return dfail(AIJHIP_ERR_ARG, "malformed CSR");
+    for (int32_t i = 0; i < m; ++i)
+        if (agg[i] < -1 || agg[i] >= n) return dfail(AIJHIP_ERR_ARG, "aggregate out of range");
+    int32_t n_cu = 0;
+    int rc = diag_device(&n_cu);
+    if (rc) return rc;
+    DCsr T, P;
+    int32_t *d_agg = nullptr;
+    double *d_p0 = nullptr, *d_dinv = nullptr;
+    hipError_t e;
+    if ((e = upload_csr(m, n, ti, tj, ta, T)) != hipSuccess || (e = upload(&d_agg, agg, m)) != hipSuccess ||
+        (e = upload(&d_p0, p0, m)) != hipSuccess || (e = upload(&d_dinv, dinv, m)) != hipSuccess)
+        rc = herr(e, "upload");
+    std::unique_ptr<aijhip_gamg_diag> h(new aijhip_gamg_diag());
+    if (!rc) rc = aijhip_gamg::prolong_from_T(T, d_agg, d_p0, d_dinv, alpha, P);
+    if (!rc) rc = download_csr(P, h.get());
+    hipFree(d_agg);
+    hipFree(d_p0);
+    hipFree(d_dinv);
+    T.release();
+    P.release();
+    if (rc) return rc;
+    *out = h.release();
+    return AIJHIP_OK;
+}
+
+int aijhip_gamg_diag_tentative(int32_t m, int32_t na, const int32_t *agg, const double *B, int32_t b_ones, double *Bc,
+                               double *p0, double *s2) {
+    if (m < 0 || na < 0 || (m > 0 && (!agg || !B || !p0)) || (na > 0 && (!Bc || !s2)))
+        return dfail(AIJHIP_ERR_ARG, "bad arguments");
+    for (int32_t i = 0; i < m; ++i)
+        if (agg[i] < -1 || agg[i] >= na) return dfail(AIJHIP_ERR_ARG, "aggregate out of range");
+    int32_t n_cu = 0;
+    int rc = diag_device(&n_cu);
+    if (rc) return rc;
+    int32_t *d_agg = nullptr;
+    double *d_B = nullptr, *d_Bc = nullptr, *d_p0 = nullptr, *d_s2 = nullptr;
+    hipError_t e;
+    if ((e = upload(&d_agg, agg, m)) == hipSuccess && (e = upload(&d_B, B, m)) == hipSuccess &&
+        (e = dalloc(&d_Bc, na)) == hipSuccess && (e = dalloc(&d_p0, m)) == hipSuccess &&
+        (e = dalloc(&d_s2, na)) == hipSuccess &&
+        // (no rows: the device routines return at once; the sums over no members are 0)
+        (e = hipMemset(d_Bc, 0, sizeof(double) * (size_t)std::max(na, 1))) == hipSuccess &&
+        (e = hipMemset(d_s2, 0, sizeof(double) * (size_t)std::max(na, 1))) == hipSuccess &&
+        (e = aijhip_gamg::tentative_device(m, na, d_agg, d_B, d_Bc, d_p0, b_ones != 0)) == hipSuccess &&
+        (e = aijhip_gamg::aggregate_sumsq_device(m, na, d_agg, d_B, d_s2, b_ones != 0)) == hipSuccess &&
+        (e = hipDeviceSynchronize()) == hipSuccess) {
+        if (m > 0) e = hipMemcpy(p0, d_p0, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && na > 0) e = hipMemcpy(Bc, d_Bc, sizeof(double) * (size_t)na, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && na > 0) e = hipMemcpy(s2, d_s2, sizeof(double) * (size_t)na, hipMemcpyDeviceToHost);
+    }
+    hipFree(d_agg);
+    hipFree(d_B);
+    hipFree(d_Bc);
+    hipFree(d_p0);
+    hipFree(d_s2);
+    return e == hipSuccess ? AIJHIP_OK : herr(e, "tentative prolongator");
+}
+
+int aijhip_gamg_diag_info(aijhip_gamg_diag_t h, int32_t *m, int32_t *n, int64_t *nz, int32_t *npasses,
+                          int32_t *p0_register) {
+    if (!h) return dfail(AIJHIP_ERR_ARG, "NULL handle");
+    if (m) *m = h->m;
+    if (n) *n = h->n;
+    if (nz) *nz = (int64_t)h->aj.size();
+    if (npasses) *npasses = (int32_t)h->trace.passes.size();
+    if (p0_register) *p0_register = h->trace.p0_register ? 1 : 0;
+    return AIJHIP_OK;
+}
+
+int aijhip_gamg_diag_get_csr(aijhip_gamg_diag_t h, int32_t *ai, int32_t *aj, double *aa) {
+    if (!h || !ai) return dfail(AIJHIP_ERR_ARG, "NULL handle");
+    std::copy(h->ai.begin(), h->ai.end(), ai);
+    if (aj) std::copy(h->aj.begin(), h->aj.end(), aj);
+    if (aa) std::copy(h->aa.begin(), h->aa.end(), aa);
+    return AIJHIP_OK;
+}
+
+int aijhip_gamg_diag_get_passes(aijhip_gamg_diag_t h, int32_t *passes, int32_t *row_table) {
+    if (!h) return dfail(AIJHIP_ERR_ARG, "NULL handle");
+    if (passes)
+        for (const ProductTrace::Pass &p : h->trace.passes) {
+            *passes++ = p.lanes;
+            *passes++ = p.table;
+            *passes++ = p.write;
+            *passes++ = p.keys_max;
+        }
+    if (row_table)
+        for (int32_t i = 0; i < h->m; ++i) row_table[i] = h->trace.row_table.empty() ? 0 : h->trace.row_table[(size_t)i];
+    return AIJHIP_OK;
+}
+
+int aijhip_gamg_diag_destroy(aijhip_gamg_diag_t h) {
+    delete h;
+    return AIJHIP_OK;
+}
+
+}  // extern "C"

@@ -14,6 +14,9 @@ GAMG_SYMBOLS = (
     "aijhip_gamg_host_level_info", "aijhip_gamg_host_get_A", "aijhip_gamg_host_get_P",
     "aijhip_gamg_host_get_aggregates", "aijhip_gamg_host_view", "aijhip_gamg_host_destroy",
     "aijhip_mg_smoother_default", "aijhip_mg_cheby_coefficients",
+    "aijhip_gamg_diag_rowprod", "aijhip_gamg_diag_rowprod_p0", "aijhip_gamg_diag_prolong",
+    "aijhip_gamg_diag_tentative", "aijhip_gamg_diag_info", "aijhip_gamg_diag_get_csr",
+    "aijhip_gamg_diag_get_passes", "aijhip_gamg_diag_destroy",
 )
 SMOOTHER_TYPES = {"richardson": 0, "chebyshev": 1}
 
@@ -55,6 +58,16 @@ def _lib():
         L.aijhip_mg_smoother_default.argtypes = [ctypes.POINTER(MgSmoother)]
         L.aijhip_mg_cheby_coefficients.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_int32,
                                                    ctypes.POINTER(ctypes.c_double), _P]
+        i32, d = ctypes.c_int32, ctypes.c_double
+        L.aijhip_gamg_diag_rowprod.argtypes = [i32, i32, i32, _P, _P, _P, _P, _P, _P, i32, ctypes.POINTER(_P)]
+        L.aijhip_gamg_diag_rowprod_p0.argtypes = [i32, i32, i32, _P, _P, _P, _P, _P, i32, ctypes.POINTER(_P)]
+        L.aijhip_gamg_diag_prolong.argtypes = [i32, i32, _P, _P, _P, _P, _P, _P, d, ctypes.POINTER(_P)]
+        L.aijhip_gamg_diag_tentative.argtypes = [i32, i32, _P, _P, i32, _P, _P, _P]
+        L.aijhip_gamg_diag_info.argtypes = [_P, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.POINTER(i32), ctypes.POINTER(i32)]
+        L.aijhip_gamg_diag_get_csr.argtypes = [_P, _P, _P, _P]
+        L.aijhip_gamg_diag_get_passes.argtypes = [_P, _P, _P]
+        L.aijhip_gamg_diag_destroy.argtypes = [_P]
         _bound = True
     return L
 
@@ -126,3 +139,94 @@ def build_host(ai, aj, aa, **params):
         return out
     finally:
         L.aijhip_gamg_host_destroy(h)
+
+
+# ---- diagnostics (include/aijhip_gamg.h "Diagnostics") ----
+
+def _csr_args(ai, aj, aa):
+    ai = np.ascontiguousarray(ai, dtype=np.int32)
+    aj = np.ascontiguousarray(aj, dtype=np.int32)
+    aa = np.ascontiguousarray(aa, dtype=np.float64)
+    if len(ai) < 1 or len(aj) != ai[-1] or len(aa) != ai[-1]:
+        raise ValueError("CSR arrays do not fit each other")
+    return ai, aj, aa
+
+
+def _diag_result(L, rc, h):
+    """(ai, aj, aa) of a diagnostic handle and what its product launched:
+    dict(passes=[(lanes, table, mode, keys_max)], row_table, p0_register,
+    shape). The handle is destroyed."""
+    _pkg._check(rc)
+    try:
+        m, n, nz, npass, reg = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        _pkg._check(L.aijhip_gamg_diag_info(h, ctypes.byref(m), ctypes.byref(n), ctypes.byref(nz), ctypes.byref(npass),
+                                            ctypes.byref(reg)))
+        ai, aj, aa = np.empty(m.value + 1, np.int32), np.empty(nz.value, np.int32), np.empty(nz.value, np.float64)
+        _pkg._check(L.aijhip_gamg_diag_get_csr(h, ai.ctypes.data, aj.ctypes.data, aa.ctypes.data))
+        passes = np.empty((npass.value, 4), np.int32)
+        row_table = np.empty(m.value, np.int32)
+        _pkg._check(L.aijhip_gamg_diag_get_passes(h, passes.ctypes.data, row_table.ctypes.data))
+        report = {"passes": [(int(g), int(t), "write" if w else "count", int(k)) for g, t, w, k in passes],
+                  "row_table": row_table, "p0_register": bool(reg.value), "shape": (m.value, n.value)}
+        return (ai, aj, aa), report
+    finally:
+        L.aijhip_gamg_diag_destroy(h)
+
+
+def device_rowprod(A, B, n, n_cu=0):
+    """C = A B through the device set-up's hash-table product. A, B: (ai, aj,
+    aa) host CSR, A m x k, B k x n. Returns ((ci, cj, ca), report)."""
+    L = _lib()
+    ai, aj, aa = _csr_args(*A)
+    bi, bj, ba = _csr_args(*B)
+    h = _P()
+    rc = L.aijhip_gamg_diag_rowprod(len(ai) - 1, len(bi) - 1, int(n), ai.ctypes.data, aj.ctypes.data, aa.ctypes.data,
+                                    bi.ctypes.data, bj.ctypes.data, ba.ctypes.data, int(n_cu), ctypes.byref(h))
+    return _diag_result(L, rc, h)
+
+
+def device_rowprod_p0(A, agg, p0, na, n_cu=0):
+    """T = A P0 through the device set-up's rowprod_p0 (P0 row j: column
+    agg[j], value p0[j], empty where agg[j] = -1). A: (ai, aj, aa), m x
+    len(agg). Returns ((ti, tj, ta), report)."""
+    L = _lib()
+    ai, aj, aa = _csr_args(*A)
+    agg = np.ascontiguousarray(agg, dtype=np.int32)
+    p0 = np.ascontiguousarray(p0, dtype=np.float64)
+    if len(agg) != len(p0):
+        raise ValueError("agg and p0 differ in length")
+    h = _P()
+    rc = L.aijhip_gamg_diag_rowprod_p0(len(ai) - 1, len(agg), int(na), ai.ctypes.data, aj.ctypes.data, aa.ctypes.data,
+                                       agg.ctypes.data, p0.ctypes.data, int(n_cu), ctypes.byref(h))
+    return _diag_result(L, rc, h)
+
+
+def device_prolong(T, n, agg, p0, dinv, alpha):
+    """P = P0 + alpha D^-1 T through prolong_from_T. T: (ti, tj, ta), m x n,
+    ascending columns. Returns (pi, pj, pa)."""
+    L = _lib()
+    ti, tj, ta = _csr_args(*T)
+    m = len(ti) - 1
+    agg = np.ascontiguousarray(agg, dtype=np.int32)
+    p0 = np.ascontiguousarray(p0, dtype=np.float64)
+    dinv = np.ascontiguousarray(dinv, dtype=np.float64)
+    if not (len(agg) == len(p0) == len(dinv) == m):
+        raise ValueError("agg, p0 and dinv have one entry per row of T")
+    h = _P()
+    rc = L.aijhip_gamg_diag_prolong(m, int(n), ti.ctypes.data, tj.ctypes.data, ta.ctypes.data, agg.ctypes.data,
+                                    p0.ctypes.data, dinv.ctypes.data, float(alpha), ctypes.byref(h))
+    return _diag_result(L, rc, h)[0]
+
+
+def device_tentative(agg, B, na, b_ones=False):
+    """(Bc, p0, s2) of tentative_device and aggregate_sumsq_device."""
+    L = _lib()
+    agg = np.ascontiguousarray(agg, dtype=np.int32)
+    B = np.ascontiguousarray(B, dtype=np.float64)
+    if len(agg) != len(B):
+        raise ValueError("agg and B differ in length")
+    Bc, p0, s2 = np.empty(int(na)), np.empty(len(agg)), np.empty(int(na))
+    rc = L.aijhip_gamg_diag_tentative(len(agg), int(na), agg.ctypes.data, B.ctypes.data, int(bool(b_ones)),
+                                      Bc.ctypes.data, p0.ctypes.data, s2.ctypes.data)
+    _pkg._check(rc)
+    return Bc, p0, s2

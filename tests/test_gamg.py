@@ -471,7 +471,8 @@ def test_gpu_device_aggregation_sweep_on_irregular_graphs(pkg, case, monkeypatch
     elif case == "random":
         m = 30000
         rng = np.random.default_rng(3)
-        r = rng.integers(0, m, size=m)  # mean degree 2 (wider Galerkin rows outgrow the device classes)
+        r = rng.integers(0, m, size=m)  # mean degree 2 (wider Galerkin rows outgrow the device classes;
+        # test_gamg_products_gpu.py runs the products at every class and past the last)
         c = rng.integers(0, m, size=m)
         keep = r != c
         ai, aj, aa = _spd_from_pattern(m, r[keep], c[keep], 2)
