@@ -23,6 +23,8 @@
  *                             -> aijhip_mat_mult_add      (w = z + A x)
  *   MatMultTranspose_SeqAIJ [ext; SURVEY §8f row 2]
  *                             -> aijhip_mat_mult_transpose (y = A^T x)
+ *   MatMatMult_SeqAIJ_SeqDense [ext; AIJ x Dense, k vectors on one operator]
+ *                             -> aijhip_mat_mat_mult      (Y = A X)
  *   MatDestroy_SeqAIJ hook, src/openacc-step2/MatDestroy_SeqAIJ.patch:18-34
  *                             -> aijhip_mat_destroy
  *
@@ -63,7 +65,8 @@ extern "C" {
  * automatic value -1 of aijhip_mpiaij_set_overlap.
  * 5: AIJHIP_OPT_ROW_TEMPLATES and AIJHIP_OPT_VALUE_CODES; aijhip_info_t's
  * former reserved0 is row_templates, and it gained value_codes (+ a
- * reserved word). */
+ * reserved word). The aijhip_mat_mat_mult* entry points were added to 5
+ * without a new version: nothing that existed changed. */
 #define AIJHIP_ABI_VERSION 5
 
 enum {
@@ -335,6 +338,46 @@ int aijhip_mat_mult_add_host(aijhip_mat_t A, const double *x, const double *z,
  * restriction). Same transposed copy and scatter order as
  * aijhip_mat_mult_transpose; the copies are pipelined as for mult_host. */
 int aijhip_mat_mult_transpose_host(aijhip_mat_t A, const double *x, double *y);
+
+/* Layouts of the dense blocks of aijhip_mat_mat_mult. */
+enum {
+    AIJHIP_DENSE_COLUMNS = 0,     /* PETSc SeqDense: X(i,j) = X[i + j*ldx], ldx >= n;
+                                     Y(i,j) = Y[i + j*ldy], ldy >= m              */
+    AIJHIP_DENSE_INTERLEAVED = 1  /* X(i,j) = X[i*ldx + j], ldx >= k;
+                                     Y(i,j) = Y[i*ldy + j], ldy >= k              */
+};
+
+/* MatMatMult_SeqAIJ_SeqDense [ext]: Y = A X, X n x k, Y m x k, device arrays,
+ * enqueued on `stream`. The matrix is read once per chunk of 8, 4, 2 or 1
+ * columns (aijhip_mat_mat_mult_chunk_widths) instead of once per column.
+ * Every Y(i,j) is the PETSc row loop's value on column j — s = 0.0, then
+ * s += aa[p] * X(aj[p], j) in storage order, each product rounded before it
+ * is added — for every plan, layout, k and leading dimension; unlike
+ * aijhip_mat_mult, rows longer than a block are summed in that order too. A
+ * row with no entries gives +0.0. Elements of Y outside the m x k block (the
+ * ld padding) are not written. X and Y must not overlap. k == 0 launches
+ * nothing. */
+int aijhip_mat_mat_mult(aijhip_mat_t A, int32_t k, int layout, const double *X, int64_t ldx,
+                        double *Y, int64_t ldy, void *stream);
+
+/* The same with host arrays (upload, multiply, download; synchronous; the
+ * copies are not pipelined with the product). */
+int aijhip_mat_mat_mult_host(aijhip_mat_t A, int32_t k, int layout, const double *X, int64_t ldx,
+                             double *Y, int64_t ldy);
+
+/* How k columns are cut into launches: widths[0..*n) from {8,4,2,1}, greedy,
+ * largest first (7 -> 4,2,1; 19 -> 8,8,2,1). Pure host function, no handle,
+ * no device. cap: the entries widths can hold; too few is AIJHIP_ERR_ARG
+ * (*n is still set). */
+int aijhip_mat_mat_mult_chunk_widths(int32_t k, int32_t *widths, int32_t cap, int32_t *n);
+
+/* What a call with (k, layout) on A's current plan does: *path = 0 generic
+ * rows, 1 CSR row blocks, 2 row templates; *n_chunks launches; *bytes = the
+ * compulsory bytes, sum over the chunks of M, plus 8 k (n + m) for X and Y,
+ * where M = 12 nz + 4 (m+1) on paths 0 and 1 and mult_layout_bytes - 8 n - 8 m
+ * of the template plan on path 2. Any out pointer may be NULL. */
+int aijhip_mat_mat_mult_get_plan(aijhip_mat_t A, int32_t k, int layout, int32_t *path,
+                                 int32_t *n_chunks, int64_t *bytes);
 
 int aijhip_mat_get_info(aijhip_mat_t A, aijhip_info_t *info);
 

@@ -40,6 +40,8 @@ WITHDRAWN_OPTIONS = {"xcd_remap": 2, "persistent": 4, "clamped": 5, "x_tile": 7,
                      "long_window": 15, "pipeline": 16}
 
 AIJHIP_OK, AIJHIP_ERR_ARG, AIJHIP_ERR_ALLOC, AIJHIP_ERR_HIP, AIJHIP_ERR_NODEVICE, AIJHIP_ERR_STATE = range(6)
+# dense block layouts of mat_mult (include/aijhip.h AIJHIP_DENSE_*)
+DENSE_LAYOUTS = {"columns": 0, "interleaved": 1}
 
 # Every symbol include/aijhip.h and include/aijhip_harness.h declare.
 ABI_SYMBOLS = (
@@ -49,6 +51,8 @@ ABI_SYMBOLS = (
     "aijhip_mat_mult_add", "aijhip_mat_mult_transpose", "aijhip_mat_mult_host",
     "aijhip_mat_mult_add_host", "aijhip_mat_mult_transpose_host",
     "aijhip_mat_get_info", "aijhip_mat_get_device_csr", "aijhip_mat_destroy",
+    "aijhip_mat_mat_mult", "aijhip_mat_mat_mult_host", "aijhip_mat_mat_mult_chunk_widths",
+    "aijhip_mat_mat_mult_get_plan",
 )
 HARNESS_SYMBOLS = (
     "aijhip_poisson_nnz", "aijhip_poisson_fill", "aijhip_poisson_vectors",
@@ -138,6 +142,10 @@ def lib() -> ctypes.CDLL:
         L.aijhip_mat_get_info.argtypes = [_P, ctypes.POINTER(AIJInfo)]
         L.aijhip_mat_get_device_csr.argtypes = [_P, ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(_P)]
         L.aijhip_mat_destroy.argtypes = [_P]
+        L.aijhip_mat_mat_mult.argtypes = [_P, ctypes.c_int32, ctypes.c_int, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]
+        L.aijhip_mat_mat_mult_host.argtypes = L.aijhip_mat_mat_mult.argtypes[:-1]
+        L.aijhip_mat_mat_mult_chunk_widths.argtypes = [ctypes.c_int32, _I32P, ctypes.c_int32, _I32P]
+        L.aijhip_mat_mat_mult_get_plan.argtypes = [_P, ctypes.c_int32, ctypes.c_int, _I32P, _I32P, _I64P]
         L.aijhip_device_count.argtypes = [ctypes.POINTER(ctypes.c_int)]
         L.aijhip_poisson_nnz.argtypes = [ctypes.c_int32] * 5 + [_I64P]
         L.aijhip_poisson_fill.argtypes = [ctypes.c_int32] * 5 + [ctypes.c_int, _P, _P, _P, _F64P]
@@ -184,6 +192,56 @@ def _stream_handle(stream) -> int:
     if isinstance(stream, int):
         return stream
     return stream.cuda_stream
+
+
+def _dense_candidates(shape, strides) -> dict:
+    """{layout: ld} for every layout a 2-D block with these strides (in
+    elements) has. A stride along an axis of length <= 1 says nothing."""
+    if len(shape) != 2 or len(strides) != 2:
+        raise TypeError(f"expected a 2-D dense block, got shape {tuple(shape)}")
+    rows, k = (int(v) for v in shape)
+    sr, sc = (int(v) for v in strides)
+    out = {}
+    if (k <= 1 or sc == 1) and (rows <= 1 or sr >= max(k, 1)):
+        out["interleaved"] = sr if rows > 1 else max(k, 1)
+    if (rows <= 1 or sr == 1) and (k <= 1 or sc >= max(rows, 1)):
+        out["columns"] = sc if k > 1 else max(rows, 1)
+    return out
+
+
+def dense_layout(shape, strides):
+    """(layout, ld) of a 2-D dense block from its shape and its strides in
+    elements: unit stride along the columns is "interleaved" with ld = the row
+    stride; unit stride along the rows is "columns" with ld = the column
+    stride. A single column (k = 1) is both: it is reported as interleaved
+    with ld = its row stride, and mat_mult pairs it with either. Anything else
+    (a view strided along both axes, rows that overlap) raises TypeError."""
+    c = _dense_candidates(shape, strides)
+    if not c:
+        raise TypeError(f"dense block of shape {tuple(shape)} with strides {tuple(strides)} is neither interleaved "
+                        "(unit stride along the columns) nor columns (unit stride along the rows)")
+    return next(iter(c.items()))
+
+
+def _common_dense_layout(xs, xst, ys, yst):
+    """The one layout the C call is given for X and Y, with their leading dimensions."""
+    cx, cy = _dense_candidates(xs, xst), _dense_candidates(ys, yst)
+    if not cx or not cy:
+        dense_layout(xs, xst)
+        dense_layout(ys, yst)
+    for name in cx:
+        if name in cy:
+            return DENSE_LAYOUTS[name], cx[name], cy[name]
+    raise TypeError(f"X is {'/'.join(cx)} and Y is {'/'.join(cy)}: mat_mult takes one layout for both")
+
+
+def chunk_widths(k: int) -> list:
+    """The launch widths MatMatMult cuts k columns into (aijhip_mat_mat_mult_chunk_widths)."""
+    n = ctypes.c_int32(0)
+    cap = max(int(k), 0) // 8 + 3
+    w = (ctypes.c_int32 * cap)()
+    _check(lib().aijhip_mat_mat_mult_chunk_widths(k, w, cap, ctypes.byref(n)))
+    return list(w[:n.value])
 
 
 def device_count() -> int:
@@ -312,6 +370,55 @@ class SeqAIJHIP:
             raise ValueError("out too short")
         _check(lib().aijhip_mat_mult_transpose_host(self._h, _np_ptr(x, np.float64), _np_ptr(y, np.float64)))
         return y
+
+    def mat_mult(self, X, Y, stream=None):
+        """Y = A X (MatMatMult_SeqAIJ_SeqDense): X (n, k), Y (m, k) float64 GPU
+        tensors, the matrix read once per chunk of up to 8 columns. Layout and
+        leading dimensions come from the strides (dense_layout): row-major
+        blocks are interleaved, column-major ones PETSc's SeqDense; padded
+        leading dimensions are fine, their padding in Y is not written."""
+        import torch
+        for t, rows, what in ((X, self.n, "X"), (Y, self.m, "Y")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda or t.dim() != 2:
+                raise TypeError(f"{what}: expected a 2-D float64 GPU tensor")
+            if t.shape[0] != rows:
+                raise ValueError(f"{what}: has {t.shape[0]} rows, needs {rows}")
+        if X.shape[1] != Y.shape[1]:
+            raise ValueError(f"X has {X.shape[1]} columns, Y has {Y.shape[1]}")
+        k = int(X.shape[1])
+        layout, ldx, ldy = (0, max(self.n, 1), max(self.m, 1)) if k == 0 else \
+            _common_dense_layout(X.shape, X.stride(), Y.shape, Y.stride())
+        _check(lib().aijhip_mat_mat_mult(self._h, k, layout, X.data_ptr(), ldx, Y.data_ptr(), ldy,
+                                         _stream_handle(stream)))
+
+    def mat_mult_host(self, X: np.ndarray, out: np.ndarray | None = None) -> np.ndarray:
+        """Y = A X with host arrays (upload, multiply, download): X (n, k)
+        float64 in C order (interleaved) or Fortran order (columns); out, when
+        given, in the same order."""
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] != self.n:
+            raise ValueError(f"X: expected shape ({self.n}, k)")
+        k = int(X.shape[1])
+        if out is None:
+            out = np.empty((self.m, k), order="F" if (X.flags["F_CONTIGUOUS"] and not X.flags["C_CONTIGUOUS"]) else "C")
+        if out.dtype != np.float64 or out.shape != (self.m, k):
+            raise ValueError(f"out: expected a float64 array of shape ({self.m}, {k})")
+        if k == 0:
+            return out
+        es = X.itemsize
+        layout, ldx, ldy = _common_dense_layout(X.shape, [s // es for s in X.strides], out.shape,
+                                                [s // es for s in out.strides])
+        _check(lib().aijhip_mat_mat_mult_host(self._h, k, layout, X.ctypes.data, ldx, out.ctypes.data, ldy))
+        return out
+
+    def mat_mult_plan(self, k: int, layout: str = "interleaved") -> dict:
+        """What mat_mult with k columns does on the current plan: path (0
+        generic rows, 1 CSR row blocks, 2 row templates), n_chunks launches and
+        the compulsory bytes they move (aijhip_mat_mat_mult_get_plan)."""
+        path, nch, nbytes = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        _check(lib().aijhip_mat_mat_mult_get_plan(self._h, int(k), DENSE_LAYOUTS.get(layout, layout),
+                                                  ctypes.byref(path), ctypes.byref(nch), ctypes.byref(nbytes)))
+        return {"path": path.value, "n_chunks": nch.value, "bytes": nbytes.value}
 
     def update_values(self, aa):
         aa = np.ascontiguousarray(aa, dtype=np.float64)

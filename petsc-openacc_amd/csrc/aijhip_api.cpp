@@ -1194,6 +1194,107 @@ int aijhip_mat_mult_transpose_host(aijhip_mat_t A, const double *x, double *y) {
     return aijhip_mat_mult_host(A->transpose, x, y);
 }
 
+namespace {
+
+// The argument checks of MatMatMult that need no device: k and the layout ...
+int matmat_check_shape(aijhip_mat_t A, int32_t k, int layout) {
+    int rc = check_handle(A);
+    if (rc) return rc;
+    if (k < 0) return fail(AIJHIP_ERR_ARG, "k is negative");
+    if (layout != AIJHIP_DENSE_COLUMNS && layout != AIJHIP_DENSE_INTERLEAVED)
+        return fail(AIJHIP_ERR_ARG, "unknown dense layout " + std::to_string(layout));
+    return AIJHIP_OK;
+}
+
+// ... and, for k > 0, the leading dimensions and the arrays
+int matmat_check_arrays(aijhip_mat_t A, int32_t k, int layout, const double *X, int64_t ldx, const double *Y,
+                        int64_t ldy) {
+    const bool il = layout == AIJHIP_DENSE_INTERLEAVED;
+    const int64_t minx = il ? k : A->n, miny = il ? k : A->m;
+    if (ldx < minx) return fail(AIJHIP_ERR_ARG, "ldx " + std::to_string(ldx) + " is below " + std::to_string(minx));
+    if (ldy < miny) return fail(AIJHIP_ERR_ARG, "ldy " + std::to_string(ldy) + " is below " + std::to_string(miny));
+    if ((int64_t)k * A->m > 0 && (!X || !Y)) return fail(AIJHIP_ERR_ARG, "NULL dense array");
+    if (X && X == Y) return fail(AIJHIP_ERR_ARG, "X and Y alias (PETSc requires distinct Mats)");
+    return AIJHIP_OK;
+}
+
+int32_t matmat_chunks(int32_t k) { return k / 8 + ((k & 4) != 0) + ((k & 2) != 0) + (k & 1); }
+
+}  // namespace
+
+int aijhip_mat_mat_mult(aijhip_mat_t A, int32_t k, int layout, const double *X, int64_t ldx, double *Y, int64_t ldy,
+                        void *stream) {
+    int rc = matmat_check_shape(A, k, layout);
+    if (rc || k == 0) return rc;
+    if ((rc = matmat_check_arrays(A, k, layout, X, ldx, Y, ldy))) return rc;
+    if (A->m == 0) return AIJHIP_OK;
+    DeviceGuard g(A->device);
+    if (g.err != hipSuccess) return hipfail(g.err, "set device");
+    const hipError_t e = aijhip::launch_spmm(*A, k, layout, X, ldx, Y, ldy, reinterpret_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hipfail(e, "MatMatMult launch");
+    return AIJHIP_OK;
+}
+
+int aijhip_mat_mat_mult_host(aijhip_mat_t A, int32_t k, int layout, const double *X, int64_t ldx, double *Y,
+                             int64_t ldy) {
+    int rc = matmat_check_shape(A, k, layout);
+    if (rc || k == 0) return rc;
+    if ((rc = matmat_check_arrays(A, k, layout, X, ldx, Y, ldy))) return rc;
+    if (A->m == 0) return AIJHIP_OK;
+    DeviceGuard g(A->device);
+    if (g.err != hipSuccess) return hipfail(g.err, "set device");
+    // tight device copies of the two blocks: `rows` runs of `run` doubles, the
+    // host arrays' leading dimensions stripped by the 2-D copies, so nothing
+    // of Y outside the m x k block is written
+    const bool il = layout == AIJHIP_DENSE_INTERLEAVED;
+    const size_t xrun = il ? (size_t)k : (size_t)A->n, xrows = il ? (size_t)A->n : (size_t)k;
+    const size_t yrun = il ? (size_t)k : (size_t)A->m, yrows = il ? (size_t)A->m : (size_t)k;
+    double *dX = nullptr, *dY = nullptr;
+    hipError_t e = hipMalloc(&dX, sizeof(double) * std::max<size_t>(1, xrun * xrows));
+    if (e == hipSuccess) e = hipMalloc(&dY, sizeof(double) * yrun * yrows);
+    if (e == hipSuccess && A->n > 0)
+        e = hipMemcpy2D(dX, sizeof(double) * xrun, X, sizeof(double) * (size_t)ldx, sizeof(double) * xrun, xrows,
+                        hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = aijhip::launch_spmm(*A, k, layout, dX, (int64_t)xrun, dY, (int64_t)yrun, nullptr);
+    if (e == hipSuccess)
+        e = hipMemcpy2D(Y, sizeof(double) * (size_t)ldy, dY, sizeof(double) * yrun, sizeof(double) * yrun, yrows,
+                        hipMemcpyDeviceToHost);
+    (void)hipFree(dX);
+    (void)hipFree(dY);
+    if (e != hipSuccess) return hipfail(e, "MatMatMult with host arrays");
+    return AIJHIP_OK;
+}
+
+int aijhip_mat_mat_mult_chunk_widths(int32_t k, int32_t *widths, int32_t cap, int32_t *n) {
+    if (k < 0) return fail(AIJHIP_ERR_ARG, "k is negative");
+    const int32_t count = matmat_chunks(k);
+    if (n) *n = count;
+    if (count > cap || (count > 0 && !widths))
+        return fail(AIJHIP_ERR_ARG, "widths holds " + std::to_string(widths ? std::max(cap, 0) : 0) + " entries, " +
+                                        std::to_string(count) + " needed");
+    for (int32_t i = 0, rem = k; rem > 0; ++i) {
+        widths[i] = aijhip::spmm_chunk_width(rem);
+        rem -= widths[i];
+    }
+    return AIJHIP_OK;
+}
+
+int aijhip_mat_mat_mult_get_plan(aijhip_mat_t A, int32_t k, int layout, int32_t *path, int32_t *n_chunks,
+                                 int64_t *bytes) {
+    int rc = matmat_check_shape(A, k, layout);
+    if (rc) return rc;
+    const int p = aijhip::spmm_path(*A);
+    const int64_t m = A->m, n = A->n, chunks = matmat_chunks(k);
+    // one pass over the matrix per chunk: the CSR arrays (paths 0 and 1), or
+    // what the template plan's MatMult streams besides its vectors
+    const int64_t M = p == aijhip::kSpmmTemplate ? aijhip::mult_layout_bytes(*A) - 8 * n - 8 * m
+                                                 : 12 * A->nz + 4 * (m + 1);
+    if (path) *path = p;
+    if (n_chunks) *n_chunks = (int32_t)chunks;
+    if (bytes) *bytes = chunks * M + 8 * (int64_t)k * (n + m);
+    return AIJHIP_OK;
+}
+
 int aijhip_mat_get_info(aijhip_mat_t A, aijhip_info_t *info) {
     int rc = check_handle(A);
     if (rc) return rc;

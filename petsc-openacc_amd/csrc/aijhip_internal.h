@@ -375,6 +375,16 @@ hipError_t launch_vector(const aijhip_mat &A, const double *x, const double *z,
 hipError_t build_transpose(const aijhip_mat &A, int32_t **d_tai, int32_t **d_taj,
                            double **d_taa, hipStream_t s);
 
+// MatMatMult, Y = A X for k dense columns (spmm.hip). What serves A's current
+// plan (aijhip_mat_mat_mult_get_plan's path) ...
+enum { kSpmmGeneric = 0, kSpmmCsr = 1, kSpmmTemplate = 2 };
+int spmm_path(const aijhip_mat &A);
+// ... the width of the next launch with `rem` > 0 columns left (8, 4, 2, 1: greedy, largest first) ...
+inline int spmm_chunk_width(int32_t rem) { return rem >= 8 ? 8 : rem >= 4 ? 4 : rem >= 2 ? 2 : 1; }
+// ... and the launches, one per chunk, each reading the matrix once.
+hipError_t launch_spmm(const aijhip_mat &A, int32_t k, int layout, const double *X, int64_t ldx, double *Y,
+                       int64_t ldy, hipStream_t s);
+
 RowList row_list(const aijhip_mat &A);
 // Per long-row segment: the column of its middle entry (synchronous).
 hipError_t segment_mid_columns(const aijhip_mat &A, const LongSeg *d_segs, int32_t n_segs, int32_t *h_out);
