@@ -155,6 +155,65 @@ int aijhip_ksp_get_pc_level(aijhip_ksp_t ksp, int32_t l, char which, int32_t *m,
  * host because a product row exceeded 256 distinct columns. */
 int aijhip_ksp_get_gamg_setup_path(aijhip_ksp_t ksp, int32_t cap, int32_t *path, int32_t *product_cols,
                                    int32_t *host_fallback);
+
+#define AIJHIP_KSP_MAX_RHS 64
+
+/* KSPMatSolve [ext]: A X = B, B and X m x k device blocks in one layout
+ * (AIJHIP_DENSE_COLUMNS / AIJHIP_DENSE_INTERLEAVED, leading dimensions as in
+ * aijhip_mat_mat_mult); elements outside the m x k blocks are neither read
+ * nor written; B and X must not overlap.
+ *
+ * k independent CG recurrences advance in lock step, one iteration at a time,
+ * the matrix read once per chunk of columns (aijhip_mat_mat_mult's chunks)
+ * instead of once per column. Columns never mix (this is not block CG): each
+ * has its own alpha, beta, norms, convergence test, reason, iteration count
+ * and history, and a column that has stopped is frozen while the others go
+ * on. The handle's tolerances, norm type, initial-guess flag and
+ * AIJHIP_KSP_POLL apply to every column. Column j's X, iteration count,
+ * reason and residual history equal, bit for bit, those of aijhip_ksp_solve
+ * on that column with the dot products in passes of their own
+ * (aijhip_ksp_get_fused = 0, e.g. an AIJHIP_KERNEL_SCALAR operator).
+ *
+ * PC none and Jacobi are served; with AIJHIP_PC_GAMG the call returns
+ * AIJHIP_ERR_STATE (the V-cycle has no multi-column form). k = 0 does nothing;
+ * k < 0 or k > AIJHIP_KSP_MAX_RHS, a NULL handle, a NULL B or X (m, k > 0), an
+ * unknown layout, a leading dimension below the minimum and overlapping
+ * blocks are AIJHIP_ERR_ARG, refused before any device work.
+ *
+ * Afterwards aijhip_ksp_get_iteration_number / _residual_norm /
+ * _converged_reason / _residual_history report column k - 1 (what PETSc's
+ * KSPMatSolve column loop leaves behind) and aijhip_ksp_get_host_syncs the
+ * polls of this solve (one per batch of iterations plus the final read). */
+int aijhip_ksp_mat_solve(aijhip_ksp_t ksp, int32_t k, int layout, const double *B, int64_t ldb,
+                         double *X, int64_t ldx, void *stream);
+/* The same with HOST blocks: upload, solve, download; synchronous. */
+int aijhip_ksp_mat_solve_host(aijhip_ksp_t ksp, int32_t k, int layout, const double *B, int64_t ldb,
+                              double *X, int64_t ldx);
+/* Per column of the last mat_solve: up to cap entries each; *k = its width.
+ * Any out pointer may be NULL. */
+int aijhip_ksp_get_mat_solve_results(aijhip_ksp_t ksp, int32_t cap, int32_t *its, int *reason,
+                                     double *rnorm, int32_t *k);
+/* Column `column`'s residual history: copies min(na, its + 1) norms; *n = that
+ * count. A column that stopped at the top of or inside iteration `its`
+ * (DIVERGED_INDEFINITE_PC, DIVERGED_INDEFINITE_MAT, beta = 0) logged no norm
+ * for it: its last entry is 0. */
+int aijhip_ksp_get_mat_solve_history(aijhip_ksp_t ksp, int32_t column, double *hist, int32_t na, int32_t *n);
+/* Compulsory HBM bytes of one lock-step iteration at width k on the set-up
+ * handle (PC none / Jacobi), with m rows and c = the number of chunks k is cut
+ * into (aijhip_mat_mat_mult_chunk_widths):
+ *   P = Z + b P with the deferred X += a P   40 m k  (reads Z, P, X; writes P, X)
+ *   W = A P                                  *spmm_bytes = aijhip_mat_mat_mult_get_plan's
+ *                                            bytes at k interleaved columns (the matrix
+ *                                            once per chunk, P in and W out once)
+ *   the p . w partials                       16 m k  (reads P, W)
+ *   R -= a W, Z = D^-1 R with their partials 32 m k  (reads R, W; writes R, Z)
+ *                                            + 8 m c (Jacobi: D^-1 once per chunk)
+ *   *bytes = *spmm_bytes + 88 m k (+ 8 m c).
+ * At k = 1 this is at least aijhip_ksp_get_iteration_bytes - 16 m: the single
+ * solver moves the same passes except that its fused dot saves the 16 m of
+ * reading P and W again (and Jacobi on row templates stores no Z). */
+int aijhip_ksp_get_mat_solve_bytes(aijhip_ksp_t ksp, int32_t k, int64_t *bytes, int64_t *spmm_bytes);
+
 int aijhip_ksp_destroy(aijhip_ksp_t ksp);
 
 #ifdef __cplusplus

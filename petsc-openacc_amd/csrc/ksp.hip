@@ -23,6 +23,7 @@
 #include "gamg_device.h"
 #include "aijhip_internal.h"
 #include "aijhip_ksp.h"
+#include "cg_multi.h"
 #include "cg_solve.h"
 #include "mg_cycle.h"
 
@@ -51,6 +52,7 @@ struct aijhip_ksp {
     // 0.392 s against 0.376 s per 400 iterations (profiles/r01/x_in_update/).
     // (Those A/B forms were withdrawn in round 4.)
     CGSolve cg;
+    CGMulti mm;  // KSPMatSolve's work vectors and per-column results (cg_multi.hip)
     aijhip_gamg_params_t gamg;
     aijhip_mg_smoother_t smoother;  // of every GAMG level but the coarsest (aijhip_ksp_set_mg_smoother)
     bool set_up = false;
@@ -85,6 +87,7 @@ void mg_free(aijhip_ksp *K) {
 void ksp_free(aijhip_ksp *K) {
     mg_free(K);
     cg_free(K->cg);
+    cgm_free(K->mm);
     hipFree(K->d_hb); hipFree(K->d_hx);
     K->d_hb = K->d_hx = nullptr;
     K->set_up = false;
@@ -551,6 +554,160 @@ int aijhip_ksp_solve_host(aijhip_ksp_t K, const double *b, double *x) {
     if ((rc = aijhip_ksp_solve(K, K->d_hb, K->d_hx, nullptr))) return rc;
     if (m > 0 && (e = hipMemcpy(x, K->d_hx, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost)) != hipSuccess)
         return cg_hip(e, "KSPSolve x out");
+    return AIJHIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// Whether an element of the m x k block at B is an element of the one at X.
+// A block is `cnt` runs of `run` doubles, ld apart (interleaved: m rows of k;
+// columns: k columns of m). With one leading dimension the test is exact, so
+// two column ranges of one wider array are distinct blocks; otherwise the
+// blocks' address ranges are compared.
+bool blocks_overlap(bool il, int64_t m, int64_t k, const double *B, int64_t ldb, const double *X, int64_t ldx) {
+    const int64_t run = il ? k : m, cnt = il ? m : k;
+    if (run <= 0 || cnt <= 0 || !B || !X) return false;
+    const intptr_t db = reinterpret_cast<intptr_t>(X) - reinterpret_cast<intptr_t>(B);
+    if (ldb == ldx && db % (intptr_t)sizeof(double) == 0) {
+        // B(i, j) = i ld + j and X(i', j') = d + i' ld + j' coincide iff
+        // (i - i') ld = d + t with t = j' - j in (-run, run)
+        const int64_t ld = ldb, d = (int64_t)(db / (intptr_t)sizeof(double));
+        const int64_t r = ((-d) % ld + ld) % ld;
+        const int64_t cand[2] = {r, r - ld};
+        for (const int64_t t : cand) {
+            if (t <= -run || t >= run) continue;
+            const int64_t q = (d + t) / ld;
+            if (q > -cnt && q < cnt) return true;
+        }
+        return false;
+    }
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(B), x0 = reinterpret_cast<uintptr_t>(X);
+    const uintptr_t be = b0 + sizeof(double) * (size_t)((cnt - 1) * ldb + run);
+    const uintptr_t xe = x0 + sizeof(double) * (size_t)((cnt - 1) * ldx + run);
+    return b0 < xe && x0 < be;
+}
+
+// KSPMatSolve's argument checks, all before any device work. *go = 0: nothing to do (k = 0).
+int mat_solve_check(aijhip_ksp_t K, int32_t k, int layout, const double *B, int64_t ldb, const double *X, int64_t ldx,
+                    int *go) {
+    *go = 0;
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    if (k < 0 || k > AIJHIP_KSP_MAX_RHS)
+        return cg_fail(AIJHIP_ERR_ARG, "k = " + std::to_string(k) + " is outside 0.." + std::to_string(AIJHIP_KSP_MAX_RHS));
+    if (layout != AIJHIP_DENSE_COLUMNS && layout != AIJHIP_DENSE_INTERLEAVED)
+        return cg_fail(AIJHIP_ERR_ARG, "unknown dense layout " + std::to_string(layout));
+    if (k == 0) return AIJHIP_OK;
+    const bool il = layout == AIJHIP_DENSE_INTERLEAVED;
+    const int64_t m = K->A->m, minld = il ? k : m;
+    if (ldb < minld) return cg_fail(AIJHIP_ERR_ARG, "ldb " + std::to_string(ldb) + " is below " + std::to_string(minld));
+    if (ldx < minld) return cg_fail(AIJHIP_ERR_ARG, "ldx " + std::to_string(ldx) + " is below " + std::to_string(minld));
+    if (m > 0 && (!B || !X)) return cg_fail(AIJHIP_ERR_ARG, "NULL dense array");
+    if (blocks_overlap(il, m, k, B, ldb, X, ldx)) return cg_fail(AIJHIP_ERR_ARG, "B and X overlap");
+    if (K->cg.pc != AIJHIP_PC_NONE && K->cg.pc != AIJHIP_PC_JACOBI)
+        return cg_fail(AIJHIP_ERR_STATE, "KSPMatSolve serves PC none and Jacobi: the V-cycle has no multi-column "
+                                         "form (solve the columns one by one with aijhip_ksp_solve)");
+    *go = 1;
+    return AIJHIP_OK;
+}
+
+int32_t mat_solve_chunks(int32_t k) { return k / 8 + ((k & 4) != 0) + ((k & 2) != 0) + (k & 1); }
+
+}  // namespace
+
+extern "C" {
+
+int aijhip_ksp_mat_solve(aijhip_ksp_t K, int32_t k, int layout, const double *B, int64_t ldb, double *X, int64_t ldx,
+                         void *stream) {
+    aijhip::Range range("KSPMatSolve");
+    int go = 0;
+    int rc = mat_solve_check(K, k, layout, B, ldb, X, ldx, &go);
+    if (rc || !go) return rc;
+    if ((rc = aijhip_ksp_set_up(K))) return rc;
+    DeviceGuard g(K->A->device);
+    K->cg.poll = 8;
+    if (const char *v = std::getenv("AIJHIP_KSP_POLL")) K->cg.poll = std::max(1, std::atoi(v));
+    return cgm_solve(K->cg, K->mm, *K->A, k, layout, B, ldb, X, ldx, reinterpret_cast<hipStream_t>(stream));
+}
+
+int aijhip_ksp_mat_solve_host(aijhip_ksp_t K, int32_t k, int layout, const double *B, int64_t ldb, double *X,
+                              int64_t ldx) {
+    int go = 0;
+    int rc = mat_solve_check(K, k, layout, B, ldb, X, ldx, &go);
+    if (rc || !go) return rc;
+    if ((rc = aijhip_ksp_set_up(K))) return rc;
+    const int64_t m = K->A->m;
+    if (m == 0) return aijhip_ksp_mat_solve(K, k, layout, B, ldb, X, ldx, nullptr);
+    DeviceGuard g(K->A->device);
+    // tight device copies of the two blocks (runs of `run` doubles, the host
+    // arrays' leading dimensions stripped by the 2-D copies): nothing of X
+    // outside its m x k block is read or written
+    const bool il = layout == AIJHIP_DENSE_INTERLEAVED;
+    const size_t run = il ? (size_t)k : (size_t)m, cnt = il ? (size_t)m : (size_t)k;
+    double *dB = nullptr, *dX = nullptr;
+    hipError_t e = hipMalloc(&dB, sizeof(double) * run * cnt);
+    if (e == hipSuccess) e = hipMalloc(&dX, sizeof(double) * run * cnt);
+    if (e == hipSuccess)
+        e = hipMemcpy2D(dB, sizeof(double) * run, B, sizeof(double) * (size_t)ldb, sizeof(double) * run, cnt,
+                        hipMemcpyHostToDevice);
+    if (e == hipSuccess && K->cg.guess_nonzero)
+        e = hipMemcpy2D(dX, sizeof(double) * run, X, sizeof(double) * (size_t)ldx, sizeof(double) * run, cnt,
+                        hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = aijhip_ksp_mat_solve(K, k, layout, dB, (int64_t)run, dX, (int64_t)run, nullptr);
+        if (!rc)
+            e = hipMemcpy2D(X, sizeof(double) * (size_t)ldx, dX, sizeof(double) * run, sizeof(double) * run, cnt,
+                            hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(dB);
+    (void)hipFree(dX);
+    if (rc) return rc;
+    return e == hipSuccess ? AIJHIP_OK : cg_hip(e, "KSPMatSolve with host arrays");
+}
+
+int aijhip_ksp_get_mat_solve_results(aijhip_ksp_t K, int32_t cap, int32_t *its, int *reason, double *rnorm,
+                                     int32_t *k) {
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    const CGMulti &mm = K->mm;
+    const int32_t n = std::min<int32_t>(std::max<int32_t>(cap, 0), mm.k);
+    for (int32_t j = 0; j < n; ++j) {
+        if (its) its[j] = mm.its[j];
+        if (reason) reason[j] = mm.reason[j];
+        if (rnorm) rnorm[j] = mm.rnorm[j];
+    }
+    if (k) *k = mm.k;
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_get_mat_solve_history(aijhip_ksp_t K, int32_t column, double *hist, int32_t na, int32_t *n) {
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    if (!n || (na > 0 && !hist)) return cg_fail(AIJHIP_ERR_ARG, "NULL argument");
+    if (column < 0 || column >= K->mm.k)
+        return cg_fail(AIJHIP_ERR_ARG, "the last mat_solve has no column " + std::to_string(column));
+    const std::vector<double> &h = K->mm.hist[column];
+    const int32_t c = std::min<int32_t>(std::max<int32_t>(na, 0), (int32_t)h.size());
+    std::copy(h.begin(), h.begin() + c, hist);
+    *n = c;
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_get_mat_solve_bytes(aijhip_ksp_t K, int32_t k, int64_t *bytes, int64_t *spmm_bytes) {
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    if (!bytes) return cg_fail(AIJHIP_ERR_ARG, "NULL argument");
+    if (k < 0 || k > AIJHIP_KSP_MAX_RHS) return cg_fail(AIJHIP_ERR_ARG, "k is outside 0..AIJHIP_KSP_MAX_RHS");
+    if (!K->set_up) return cg_fail(AIJHIP_ERR_STATE, "KSP is not set up");
+    if (K->cg.pc != AIJHIP_PC_NONE && K->cg.pc != AIJHIP_PC_JACOBI)
+        return cg_fail(AIJHIP_ERR_STATE, "KSPMatSolve serves PC none and Jacobi: the V-cycle has no multi-column form");
+    int64_t sp = 0;
+    const int rc = aijhip_mat_mat_mult_get_plan(K->A, k, AIJHIP_DENSE_INTERLEAVED, nullptr, nullptr, &sp);
+    if (rc) return rc;
+    // km_aypx 40 m k (reads Z, P, X; writes P, X), km_dot 16 m k (reads P, W),
+    // km_update 32 m k (reads R, W; writes R, Z) and, Jacobi, D^-1 once per chunk
+    const int64_t m = K->A->m;
+    const int64_t vec = 88 * m * k + (K->cg.pc == AIJHIP_PC_JACOBI ? 8 * m * mat_solve_chunks(k) : 0);
+    *bytes = sp + vec;
+    if (spmm_bytes) *spmm_bytes = sp;
     return AIJHIP_OK;
 }
 

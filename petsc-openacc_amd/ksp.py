@@ -30,7 +30,10 @@ KSP_SYMBOLS = (
     "aijhip_ksp_set_gamg_params", "aijhip_ksp_get_pc_levels", "aijhip_ksp_get_pc_level",
     "aijhip_ksp_get_gamg_setup_path", "aijhip_ksp_get_host_syncs", "aijhip_ksp_get_iteration_bytes",
     "aijhip_ksp_solve_host", "aijhip_ksp_set_mg_smoother", "aijhip_ksp_get_mg_smoother",
+    "aijhip_ksp_mat_solve", "aijhip_ksp_mat_solve_host", "aijhip_ksp_get_mat_solve_results",
+    "aijhip_ksp_get_mat_solve_history", "aijhip_ksp_get_mat_solve_bytes",
 )
+KSP_MAX_RHS = 64  # AIJHIP_KSP_MAX_RHS
 _P = ctypes.c_void_p
 _bound = False
 
@@ -68,6 +71,13 @@ def _lib():
         L.aijhip_ksp_get_pc_levels.argtypes = [_P, ctypes.POINTER(ctypes.c_int32), _P, _P, ctypes.c_int32,
                                                ctypes.POINTER(ctypes.c_double)]
         L.aijhip_ksp_get_gamg_setup_path.argtypes = [_P, ctypes.c_int32, _P, _P, ctypes.POINTER(ctypes.c_int32)]
+        L.aijhip_ksp_mat_solve.argtypes = [_P, ctypes.c_int32, ctypes.c_int, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]
+        L.aijhip_ksp_mat_solve_host.argtypes = L.aijhip_ksp_mat_solve.argtypes[:-1]
+        L.aijhip_ksp_get_mat_solve_results.argtypes = [_P, ctypes.c_int32, _P, _P, _P, ctypes.POINTER(ctypes.c_int32)]
+        L.aijhip_ksp_get_mat_solve_history.argtypes = [_P, ctypes.c_int32, _P, ctypes.c_int32,
+                                                       ctypes.POINTER(ctypes.c_int32)]
+        L.aijhip_ksp_get_mat_solve_bytes.argtypes = [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
+                                                     ctypes.POINTER(ctypes.c_int64)]
         _bound = True
     return L
 
@@ -114,6 +124,78 @@ class KSPCG:
         if x.dtype != np.float64 or not x.flags["C_CONTIGUOUS"] or len(x) < self.A.m or len(b) < self.A.m:
             raise TypeError("solve_host: contiguous float64 arrays of the operator's size")
         _pkg._check(_lib().aijhip_ksp_solve_host(self._h, b.ctypes.data, x.ctypes.data))
+
+    def _mat_solve_layout(self, bshape, bstrides, xshape, xstrides):
+        """(k, layout, ldb, ldx) of a mat_solve's blocks from their shapes and
+        strides in elements, checked before any library call."""
+        bshape, xshape = tuple(int(v) for v in bshape), tuple(int(v) for v in xshape)
+        if len(bshape) != 2 or len(xshape) != 2:
+            raise TypeError("mat_solve: B and X are 2-D blocks of shape (m, k)")
+        if bshape != xshape or bshape[0] != self.A.m:
+            raise TypeError(f"mat_solve: B is {bshape} and X is {xshape}, both must be ({self.A.m}, k)")
+        k = bshape[1]
+        if k > KSP_MAX_RHS:
+            raise ValueError(f"mat_solve: k = {k} is above AIJHIP_KSP_MAX_RHS = {KSP_MAX_RHS}")
+        if k == 0:
+            return 0, 1, 1, 1
+        layout, ldb, ldx = _pkg._common_dense_layout(bshape, bstrides, xshape, xstrides)
+        return k, layout, ldb, ldx
+
+    def mat_solve(self, B, X, stream=None):
+        """KSPMatSolve (aijhip_ksp_mat_solve): A X = B for float64 GPU tensors
+        of shape (m, k), k <= 64, the columns solved as independent CG
+        recurrences in lock step (PC none / Jacobi). Layout and leading
+        dimensions come from the strides as in SeqAIJHIP.mat_mult; B and X take
+        one layout. X is overwritten (read first with a nonzero initial guess)."""
+        import torch
+        for t, what in ((B, "B"), (X, "X")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise TypeError(f"mat_solve: {what} must be a float64 torch tensor on the GPU")
+        k, layout, ldb, ldx = self._mat_solve_layout(B.shape, B.stride(), X.shape, X.stride())
+        if not (B.is_cuda and X.is_cuda):
+            raise TypeError("mat_solve: B and X must be on the GPU")
+        _pkg._check(_lib().aijhip_ksp_mat_solve(self._h, k, layout, B.data_ptr(), ldb, X.data_ptr(), ldx,
+                                                _pkg._stream_handle(stream)))
+
+    def mat_solve_host(self, B: np.ndarray, X: np.ndarray):
+        """KSPMatSolve with host arrays (aijhip_ksp_mat_solve_host): float64
+        arrays of shape (m, k) in one order (C: interleaved, Fortran: columns)."""
+        for a, what in ((B, "B"), (X, "X")):
+            if not isinstance(a, np.ndarray) or a.dtype != np.float64:
+                raise TypeError(f"mat_solve_host: {what} must be a float64 numpy array")
+        es = B.itemsize
+        k, layout, ldb, ldx = self._mat_solve_layout(B.shape, [s // es for s in B.strides], X.shape,
+                                                     [s // es for s in X.strides])
+        _pkg._check(_lib().aijhip_ksp_mat_solve_host(self._h, k, layout, B.ctypes.data, ldb, X.ctypes.data, ldx))
+
+    def mat_results(self) -> list:
+        """[(its, reason, rnorm)] per column of the last mat_solve."""
+        k = ctypes.c_int32()
+        L = _lib()
+        _pkg._check(L.aijhip_ksp_get_mat_solve_results(self._h, 0, None, None, None, ctypes.byref(k)))
+        its = np.zeros(max(k.value, 1), np.int32)
+        reason = np.zeros(max(k.value, 1), np.intc)
+        rnorm = np.zeros(max(k.value, 1), np.float64)
+        _pkg._check(L.aijhip_ksp_get_mat_solve_results(self._h, k.value, its.ctypes.data, reason.ctypes.data,
+                                                       rnorm.ctypes.data, ctypes.byref(k)))
+        return [(int(its[j]), int(reason[j]), float(rnorm[j])) for j in range(k.value)]
+
+    def mat_history(self, j: int) -> np.ndarray:
+        """Column j's residual history of the last mat_solve."""
+        n = ctypes.c_int32()
+        L = _lib()
+        _pkg._check(L.aijhip_ksp_get_mat_solve_history(self._h, int(j), None, 0, ctypes.byref(n)))
+        its = self.mat_results()[int(j)][0]
+        buf = np.empty(its + 1)
+        _pkg._check(L.aijhip_ksp_get_mat_solve_history(self._h, int(j), buf.ctypes.data, len(buf), ctypes.byref(n)))
+        return buf[: n.value]
+
+    def mat_solve_bytes(self, k: int):
+        """(total, MatMatMult part): compulsory HBM bytes of one lock-step
+        iteration at width k on the set-up solver (aijhip_ksp_get_mat_solve_bytes)."""
+        t, sp = ctypes.c_int64(), ctypes.c_int64()
+        _pkg._check(_lib().aijhip_ksp_get_mat_solve_bytes(self._h, int(k), ctypes.byref(t), ctypes.byref(sp)))
+        return t.value, sp.value
 
     @property
     def its(self) -> int:
