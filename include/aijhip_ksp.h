@@ -174,8 +174,12 @@ int aijhip_ksp_get_gamg_setup_path(aijhip_ksp_t ksp, int32_t cap, int32_t *path,
  * on that column with the dot products in passes of their own
  * (aijhip_ksp_get_fused = 0, e.g. an AIJHIP_KERNEL_SCALAR operator).
  *
- * PC none and Jacobi are served; with AIJHIP_PC_GAMG the call returns
- * AIJHIP_ERR_STATE (the V-cycle has no multi-column form). k = 0 does nothing;
+ * PC none and Jacobi are served, and AIJHIP_PC_GAMG on a handle with a reserved
+ * V-cycle width (aijhip_ksp_set_mat_vcycle_width, k within it): one
+ * multi-column V-cycle per iteration, on all k columns until every column
+ * has stopped (a stopped column's X, R, P and state stay frozen). Without a
+ * reserved width a GAMG handle returns AIJHIP_ERR_STATE (the V-cycle has no
+ * multi-column form), with k above it AIJHIP_ERR_STATE naming both. k = 0 does nothing;
  * k < 0 or k > AIJHIP_KSP_MAX_RHS, a NULL handle, a NULL B or X (m, k > 0), an
  * unknown layout, a leading dimension below the minimum and overlapping
  * blocks are AIJHIP_ERR_ARG, refused before any device work.
@@ -211,8 +215,48 @@ int aijhip_ksp_get_mat_solve_history(aijhip_ksp_t ksp, int32_t column, double *h
  *   *bytes = *spmm_bytes + 88 m k (+ 8 m c).
  * At k = 1 this is at least aijhip_ksp_get_iteration_bytes - 16 m: the single
  * solver moves the same passes except that its fused dot saves the 16 m of
- * reading P and W again (and Jacobi on row templates stores no Z). */
+ * reading P and W again (and Jacobi on row templates stores no Z).
+ *
+ * A GAMG handle with a reserved width (k within it): *spmm_bytes = the CG
+ * product and every product of the V-cycle at its
+ * aijhip_mat_mat_mult_get_plan bytes (per smoothed level A_l 2 its times for
+ * Richardson(its), 2 its + 2 for Chebyshev(its), P and P^T once), and
+ *   CG's vector passes                        96 m k  (40 + 16 as above; R -= a W 24:
+ *                                             reads R, W, writes R; the Z.Z, Z.R
+ *                                             partials 16: reads Z, R)
+ *   per level of m_l rows, x = f D^-1 b       16 m_l k + 8 m_l (the smoothers' start,
+ *                                             the coarse solve)
+ *   per smoothed level, the row operands the epilogues read beyond a product's
+ *   own X and Y: residual 8 m_l k (b), interpolation 8 m_l k (x), a Richardson
+ *   step 8 m_l k + 8 m_l c (b, D^-1 once per chunk), a Chebyshev step the same
+ *   + 8 m_l k where it reads p_km1 (all but the first going down).
+ * The matrices count once per chunk, so bytes(8) < 8 bytes(1). */
 int aijhip_ksp_get_mat_solve_bytes(aijhip_ksp_t ksp, int32_t k, int64_t *bytes, int64_t *spmm_bytes);
+
+/* The width the multi-column V-cycle is reserved for, 0 <= kmax <=
+ * AIJHIP_KSP_MAX_RHS (default 0: KSPMatSolve and PCMatApply refuse a GAMG
+ * handle). With kmax > 0 the hierarchy's level blocks (b, x, r, w of every
+ * level, m_l x kmax) and KSPMatSolve's work vectors for kmax columns are
+ * allocated at set-up; on a handle that is set up the call allocates them at
+ * once and leaves the hierarchy as it is. A solve then allocates nothing
+ * (the histories regrow only when max_it was raised). */
+int aijhip_ksp_set_mat_vcycle_width(aijhip_ksp_t ksp, int32_t kmax);
+int aijhip_ksp_get_mat_vcycle_width(aijhip_ksp_t ksp, int32_t *kmax);
+
+/* PCApply [ext]: z = M^-1 r for the handle's PC (none: z = r; Jacobi:
+ * z = D^-1 r; GAMG: one V-cycle), device vectors of m entries that do not
+ * alias; sets the handle up if it is not. */
+int aijhip_ksp_pc_apply(aijhip_ksp_t ksp, const double *r, double *z, void *stream);
+/* PCMatApply [ext]: Z = M^-1 R for m x k device blocks in one layout, with
+ * aijhip_ksp_mat_solve's argument checks and refusals (a GAMG handle needs a
+ * reserved width of at least k). Column j of Z equals aijhip_ksp_pc_apply on
+ * column j bit for bit wherever no level operator, P or P^T has a row of more
+ * than 128 entries (longer rows are summed in another order by the
+ * single-vector launches). For GAMG, blocks that are not tight interleaved
+ * (columns layout, padded leading dimension) go through the handle's tight
+ * interleaved blocks. Nothing outside the m x k block of Z is written. */
+int aijhip_ksp_pc_mat_apply(aijhip_ksp_t ksp, int32_t k, int layout, const double *R, int64_t ldr, double *Z,
+                            int64_t ldz, void *stream);
 
 int aijhip_ksp_destroy(aijhip_ksp_t ksp);
 

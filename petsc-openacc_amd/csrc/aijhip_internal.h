@@ -381,9 +381,25 @@ enum { kSpmmGeneric = 0, kSpmmCsr = 1, kSpmmTemplate = 2 };
 int spmm_path(const aijhip_mat &A);
 // ... the width of the next launch with `rem` > 0 columns left (8, 4, 2, 1: greedy, largest first) ...
 inline int spmm_chunk_width(int32_t rem) { return rem >= 8 ? 8 : rem >= 4 ? 4 : rem >= 2 ? 2 : 1; }
-// ... and the launches, one per chunk, each reading the matrix once.
+// ... what a launch does with the sums s = A X (interleaved blocks only beyond
+// plain; per row o and column j, parenthesised as written, nothing contracted):
+//   plain  Y = s
+//   add    Y = B + A X, the sum started from B(o, j) (MatMultAdd; B may be Y)
+//   resid  Y = B + (-1) s
+//   post   Y = X + c2 (dinv_o (B + (-1) s))              (square A, Y != X)
+//   cheby  Y = (c0 PM1 + c1 X) + c2 (dinv_o (B + (-1) s)), PM1 NULL: c1 X + ...
+//          (square A; Y may be PM1, never X)
+// B and PM1 are laid out as Y (leading dimension ldy) ...
+enum { kSpmmPlain = 0, kSpmmAdd, kSpmmResid, kSpmmPost, kSpmmCheby };
+struct SpmmOp {
+    int op = kSpmmPlain;
+    const double *B = nullptr, *PM1 = nullptr, *dinv = nullptr;
+    double c0 = 0.0, c1 = 0.0, c2 = 1.0;
+};
+// ... and the launches, one per chunk, each reading the matrix once. stop: a
+// device flag; every workgroup returns at once when it is set.
 hipError_t launch_spmm(const aijhip_mat &A, int32_t k, int layout, const double *X, int64_t ldx, double *Y,
-                       int64_t ldy, hipStream_t s);
+                       int64_t ldy, hipStream_t s, const SpmmOp &op = SpmmOp(), const int *stop = nullptr);
 
 RowList row_list(const aijhip_mat &A);
 // Per long-row segment: the column of its middle entry (synchronous).

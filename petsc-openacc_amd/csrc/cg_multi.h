@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "cg_solve.h"
+#include "mg_cycle.h"
 
 // The lock-step work vectors (m x k interleaved, leading dimension = the
 // solve's k), the per-column partial lists, states and histories, and the
@@ -34,10 +35,24 @@ struct CGMulti {
     std::vector<std::vector<double>> hist;
 };
 
+// The handle's GAMG hierarchy and its multi-column level blocks (mg_cycle.h)
+struct CGMultiPC {
+    const std::vector<aijhip::MGLevelView> *lv;
+    const aijhip::MGMultiBlocks *mb;
+};
+
 void cgm_free(CGMulti &mm);
+// The work vectors for k columns (cgm_solve calls it; a handle with a reserved
+// V-cycle width calls it at set-up, so that its solves allocate nothing).
+int cgm_reserve(const CGSolve &cg, CGMulti &mm, int32_t k);
+// dst = src for an m x k block between layouts / leading dimensions (sil, dil:
+// interleaved), one lane per entry, on s.
+void cgm_copy_block(int64_t m, int32_t k, int n_cu, const double *src, int64_t lds, bool sil, double *dst,
+                    int64_t ldd, bool dil, hipStream_t s);
 // A X = B for k columns on s with cg's tolerances, norm type, initial-guess
-// flag, poll and PC (none / Jacobi; cg must be set up for A). B and X are
-// checked by the caller. The per-column results land in mm, column k - 1's
+// flag, poll and PC (none / Jacobi, or with mg the GAMG V-cycle on blocks
+// reserved for k columns; cg must be set up for A). B and X are checked by
+// the caller. The per-column results land in mm, column k - 1's
 // and the polls also in cg (its, reason, rnorm, hist, waits).
 int cgm_solve(CGSolve &cg, CGMulti &mm, const aijhip_mat &A, int32_t k, int layout, const double *B, int64_t ldb,
-              double *X, int64_t ldx, hipStream_t s);
+              double *X, int64_t ldx, hipStream_t s, const CGMultiPC *mg = nullptr);

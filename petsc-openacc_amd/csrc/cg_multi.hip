@@ -1,6 +1,6 @@
 // cg_multi.hip — KSPMatSolve [ext]: A X = B for a block of k right-hand
-// sides as k independent preconditioned CG recurrences (PC none / Jacobi)
-// advanced in lock step, so that one iteration reads the matrix once per chunk
+// sides as k independent preconditioned CG recurrences (PC none / Jacobi, or
+// GAMG through the multi-column V-cycle, mg_cycle.h) advanced in lock step, so that one iteration reads the matrix once per chunk
 // of columns (launch_spmm) instead of once per column. Columns never mix: each
 // has its own CGState (alpha, beta, norms, reason, its) and history, and a
 // column that has stopped is frozen while the others go on.
@@ -19,7 +19,11 @@
 //
 // Per iteration: km_aypx, launch_spmm (W = A P, W in Z's storage), km_dot,
 // km_sum_dpi, km_update, km_sum_iter; km_all_done once per batch sets the flag
-// the host polls. The work vectors R, Z/W and P are m x k interleaved with
+// the host polls and the product stops at. With GAMG (cg_solve.hip's order):
+// km_update writes R and the R.R partials only, mg_vcycle_multi gives Z = M^-1 R
+// for all k columns until every column has stopped, km_dots (k_dots' order) the
+// Z.Z and Z.R partials, and km_all_done runs after every iteration, so that the
+// V-cycles of a finished solve's last batch return at once. The work vectors R, Z/W and P are m x k interleaved with
 // leading dimension k; the chunks are launch_spmm's (spmm_chunk_width).
 #include "cg_multi.h"
 
@@ -146,7 +150,9 @@ __host__ __device__ __forceinline__ double *part_of(double *part, int nb, int c,
 
 // k_init for W columns: r = b (zero guess, x = 0) or r = b - A x (ax holds
 // A x), z = D^-1 r, the partials of Z.Z, Z.R, R.R and of |D^-1 b|^2 or |b|^2.
-// r, z, part: at the chunk's first column.
+// r, z, part: at the chunk's first column. With GAMG this is PC none's pass
+// (R, the R.R partials and |b|^2 as k_init's GAMG form has them); the V-cycle
+// and km_dots then overwrite Z and the Z.Z, Z.R (and |M^-1 b|^2) partials.
 template <int W, bool IL, bool V2>
 __global__ __launch_bounds__(kVecThreads) void km_init(int64_t n, int64_t ld, Blk<IL> B, Blk<IL> X, Blk<IL> AX,
                                                        double *r, double *z, const double *__restrict__ dinv,
@@ -268,7 +274,7 @@ __global__ __launch_bounds__(kVecThreads) void km_update(int64_t n, int64_t ld, 
     unsigned live, later;
     chunk_state<W>(S, a, bb, live, later);
     if (!live) return;
-    const bool jac = pc == AIJHIP_PC_JACOBI;
+    const bool jac = pc == AIJHIP_PC_JACOBI, gamg = pc == AIJHIP_PC_GAMG;
     double acc[3 * W] = {};  // zz, zr, rr of column c at 3 c + 0..2
     GRID_STRIDE(i, n) {
         double rv[W], wv[W];
@@ -287,11 +293,53 @@ __global__ __launch_bounds__(kVecThreads) void km_update(int64_t n, int64_t ld, 
             acc[3 * c + 1] += zi * ri;
         }
         st_row<W, V2>(r + i * ld, rv, live);
-        st_row<W, V2>(wz + i * ld, wv, live);
+        if (!gamg) st_row<W, V2>(wz + i * ld, wv, live);
     }
+    // GAMG (k_update's form): R and the R.R partials only; Z and the Z.Z, Z.R
+    // partials follow from the V-cycle and km_dots
     const double s = block_sums<3 * W>(acc, scratch);
     const int t = threadIdx.x;
-    if (t < 3 * W && ((live >> (t / 3)) & 1u)) part_of(part, gridDim.x, t / 3, t % 3)[blockIdx.x] = s;
+    if (t < 3 * W && ((live >> (t / 3)) & 1u) && (!gamg || t % 3 == 2))
+        part_of(part, gridDim.x, t / 3, t % 3)[blockIdx.x] = s;
+}
+
+// k_dots for W columns: the partials of a.a into slot sa and of a.c into slot
+// sc (sc < 0: skip) of each live column (S NULL: every column), in k_dots'
+// order: the same lanes own the same rows, each quantity through bsum's tree
+template <int W, bool V2>
+__global__ __launch_bounds__(kVecThreads) void km_dots(int64_t n, int64_t ld, const double *a, const double *c,
+                                                       double *part, int sa, int sc, const CGState *S) {
+    __shared__ double scratch[2 * W * (kVecThreads / 64)];
+    unsigned live = 0;
+#pragma unroll
+    for (int q = 0; q < W; ++q)
+        if (!S || !S[q].done) live |= 1u << q;
+    if (!live) return;
+    double acc[2 * W] = {};  // aa, ac of column q at 2 q + 0..1
+    GRID_STRIDE(i, n) {
+        double av[W], cv[W];
+        ld_row<W, V2>(a + i * ld, av);
+        if (sc >= 0) ld_row<W, V2>(c + i * ld, cv);
+#pragma unroll
+        for (int q = 0; q < W; ++q) {
+            acc[2 * q] += av[q] * av[q];
+            if (sc >= 0) acc[2 * q + 1] += av[q] * cv[q];
+        }
+    }
+    const double s = block_sums<2 * W>(acc, scratch);
+    const int t = threadIdx.x;
+    if (t < 2 * W && ((live >> (t >> 1)) & 1u) && ((t & 1) == 0 || sc >= 0))
+        part_of(part, gridDim.x, t >> 1, (t & 1) ? sc : sa)[blockIdx.x] = s;
+}
+
+// A block into another layout or leading dimension (B for the V-cycle's tight
+// interleaved form, PCMatApply's blocks): one lane per entry
+__global__ __launch_bounds__(kVecThreads) void km_copy(int64_t m, int32_t k, const double *src, int64_t lds, int sil,
+                                                       double *dst, int64_t ldd, int dil) {
+    GRID_STRIDE(t, m * k) {
+        const int64_t i = t / k, j = t % k;
+        dst[dil ? i * ldd + j : i + j * ldd] = src[sil ? i * lds + j : i + j * lds];
+    }
 }
 
 // k_final_x for W columns: the last X += a P of every column whose xpend is set
@@ -395,6 +443,23 @@ struct MultiRun {
     double *X;
     int64_t ldx;
     hipStream_t s;
+    const CGMultiPC *mg;  // the GAMG V-cycle (NULL: PC none / Jacobi)
+
+    // Z = M^-1 R on the k columns of two tight interleaved blocks
+    int vcycle(const double *r, double *z, const int *stop) const {
+        return aijhip::mg_vcycle_multi(*mg->lv, *mg->mb, k, r, z, s, stop);
+    }
+    // the partials of a.a (slot sa) and a.c (slot sc) of every live column
+    void dots(const double *a, const double *c, int sa, int sc, bool masked) const {
+        const int nb = mm.nb;
+        chunks([&](auto W, auto, auto V2, int32_t j0) {
+            constexpr int w = decltype(W)::value;
+            constexpr bool v2 = decltype(V2)::value;
+            hipLaunchKernelGGL((km_dots<w, v2>), dim3(nb), dim3(kVecThreads), 0, s, (int64_t)cg.m, (int64_t)k, a + j0,
+                               c ? c + j0 : nullptr, part_of(mm.d_part, nb, j0, 0), sa, sc,
+                               masked ? mm.d_state + j0 : nullptr);
+        });
+    }
 
     // f(W, IL, V2, j0) for every chunk of the k columns. 16-byte accesses only
     // where every address they are issued at is 16-byte aligned: the work
@@ -432,7 +497,8 @@ int multi_iteration(const MultiRun &R, const CGParams &p) {
                            R.blk<il>(R.X, R.ldx, j0), mm.d_state + j0);
     });
     // W = A P for all columns (W shares Z's storage); frozen columns' W is never read
-    const hipError_t e = aijhip::launch_spmm(R.A, R.k, AIJHIP_DENSE_INTERLEAVED, mm.d_p, ld, mm.d_z, ld, s);
+    const hipError_t e = aijhip::launch_spmm(R.A, R.k, AIJHIP_DENSE_INTERLEAVED, mm.d_p, ld, mm.d_z, ld, s,
+                                             aijhip::SpmmOp(), mm.d_flag);
     if (e != hipSuccess) return cg_hip(e, "KSPMatSolve product");
     R.chunks([&](auto W, auto, auto V2, int32_t j0) {
         constexpr int w = decltype(W)::value;
@@ -447,13 +513,22 @@ int multi_iteration(const MultiRun &R, const CGParams &p) {
         hipLaunchKernelGGL((km_update<w, v2>), vg, vt, 0, s, m, ld, mm.d_r + j0, mm.d_z + j0, cg.d_dinv,
                            part_of(mm.d_part, nb, j0, 0), mm.d_state + j0, cg.pc);
     });
+    if (R.mg) {  // Z = M^-1 R on every column until all have stopped, then k_dots' Z.Z and Z.R
+        if (const int rc = R.vcycle(mm.d_r, mm.d_z, mm.d_flag)) return rc;
+        R.dots(mm.d_z, mm.d_r, 0, 1, true);
+    }
     hipLaunchKernelGGL(km_sum_iter, kg, rt, 0, s, mm.d_part, nb, mm.d_state, mm.d_hist, mm.hist_cap, p);
+    // with a V-cycle the flag is set after every iteration, so that the rest of a
+    // batch costs launches only; PC none / Jacobi: once per batch (cgm_solve)
+    if (R.mg) hipLaunchKernelGGL(km_all_done, dim3(1), dim3(64), 0, s, mm.d_state, R.k, mm.d_flag);
     const hipError_t e2 = hipGetLastError();
     return e2 == hipSuccess ? AIJHIP_OK : cg_hip(e2, "KSPMatSolve iteration");
 }
 
+}  // namespace
+
 // The work vectors for k columns of m rows and histories of cg.max_it + 2 entries
-int multi_reserve(const CGSolve &cg, CGMulti &mm, int32_t k) {
+int cgm_reserve(const CGSolve &cg, CGMulti &mm, int32_t k) {
     const int32_t hcap = cg.max_it + 2;
     if (mm.cap_k >= k && mm.hist_cap >= hcap && mm.m == cg.m && mm.nb == cg.vec_grid) return AIJHIP_OK;
     const int32_t cap = std::max(k, mm.cap_k);
@@ -478,7 +553,14 @@ int multi_reserve(const CGSolve &cg, CGMulti &mm, int32_t k) {
     return AIJHIP_OK;
 }
 
-}  // namespace
+void cgm_copy_block(int64_t m, int32_t k, int n_cu, const double *src, int64_t lds, bool sil, double *dst,
+                    int64_t ldd, bool dil, hipStream_t s) {
+    const int64_t n = m * k;
+    if (n <= 0) return;
+    const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + kVecThreads - 1) / kVecThreads,
+                                                                  (int64_t)std::max(n_cu, 1) * 8)));
+    hipLaunchKernelGGL(km_copy, g, dim3(kVecThreads), 0, s, m, k, src, lds, sil ? 1 : 0, dst, ldd, dil ? 1 : 0);
+}
 
 void cgm_free(CGMulti &mm) {
     hipFree(mm.d_r); hipFree(mm.d_z); hipFree(mm.d_p); hipFree(mm.d_part); hipFree(mm.d_hist);
@@ -494,13 +576,15 @@ void cgm_free(CGMulti &mm) {
 }
 
 int cgm_solve(CGSolve &cg, CGMulti &mm, const aijhip_mat &A, int32_t k, int layout, const double *B, int64_t ldb,
-              double *X, int64_t ldx, hipStream_t s) {
-    int rc = multi_reserve(cg, mm, k);
+              double *X, int64_t ldx, hipStream_t s, const CGMultiPC *mg) {
+    if ((cg.pc == AIJHIP_PC_GAMG) != (mg != nullptr))
+        return cg_fail(AIJHIP_ERR_STATE, "KSPMatSolve: the V-cycle goes with PC GAMG");
+    int rc = cgm_reserve(cg, mm, k);
     if (rc) return rc;
     const int64_t m = cg.m, ld = k;
     const bool il = layout == AIJHIP_DENSE_INTERLEAVED;
     const CGParams p{cg.rtol, cg.abstol, cg.dtol, cg.max_it, cg.normtype, cg.guess_nonzero ? 0 : 1, cg.pc};
-    const MultiRun R{cg, mm, A, k, il, B, ldb, X, ldx, s};
+    const MultiRun R{cg, mm, A, k, il, B, ldb, X, ldx, s, mg};
     const int nb = mm.nb;
     const dim3 vg(nb), vt(kVecThreads), rt(kRedThreads), kg(k);
     hipError_t e = hipSuccess;
@@ -521,6 +605,22 @@ int cgm_solve(CGSolve &cg, CGMulti &mm, const aijhip_mat &A, int32_t k, int layo
                            R.blk<cil>(mm.d_p, ldax, j0), mm.d_r + j0, mm.d_z + j0, cg.d_dinv,
                            part_of(mm.d_part, nb, j0, 0), p);
     });
+    if (mg) {
+        // cg_solve's order; no stop flag yet (the first scalar step initialises the states)
+        if (cg.guess_nonzero && cg.normtype != AIJHIP_KSP_NORM_UNPRECONDITIONED) {
+            // snorm = |M^-1 b| per column: the V-cycle on B, through the finest
+            // staging block when B is not tight interleaved
+            const double *bt = B;
+            if (!il || ldb != ld) {
+                cgm_copy_block(m, k, A.n_cu, B, ldb, il, mg->mb->lev[0].b, ld, true, s);
+                bt = mg->mb->lev[0].b;
+            }
+            if ((rc = R.vcycle(bt, mm.d_z, nullptr))) return rc;
+            R.dots(mm.d_z, nullptr, 3, -1, false);
+        }
+        if ((rc = R.vcycle(mm.d_r, mm.d_z, nullptr))) return rc;
+        R.dots(mm.d_z, mm.d_r, 0, 1, false);
+    }
     hipLaunchKernelGGL(km_sum_init, kg, rt, 0, s, mm.d_part, nb, mm.d_state, mm.d_hist, mm.hist_cap, p);
     hipLaunchKernelGGL(km_all_done, dim3(1), dim3(64), 0, s, mm.d_state, k, mm.d_flag);
     if ((e = hipGetLastError()) != hipSuccess) return cg_hip(e, "KSPMatSolve init");

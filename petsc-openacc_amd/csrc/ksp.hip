@@ -63,6 +63,8 @@ struct aijhip_ksp {
     double *d_hb = nullptr, *d_hx = nullptr;  // aijhip_ksp_solve_host's device copies of b and x
     std::vector<MGLevel> mg;                  // GAMG levels, finest first
     std::vector<aijhip::MGLevelView> mgview;  // what the V-cycle walks (mg_cycle.h)
+    int32_t mat_vcycle = 0;     // columns the multi-column V-cycle is reserved for (0: KSPMatSolve refuses GAMG)
+    aijhip::MGMultiBlocks mgm;  // its level blocks (aijhip_ksp_set_mat_vcycle_width)
     double *d_mgpart = nullptr;               // fused finest-level z.z / z.r partials
     double setup_seconds = 0.0;
     // how each level's coarsening was built (aijhip_ksp_get_gamg_setup_path)
@@ -80,6 +82,7 @@ void mg_free(aijhip_ksp *K) {
     }
     K->mg.clear();
     K->mgview.clear();
+    aijhip::mg_multi_free(K->mgm);
     hipFree(K->d_mgpart);
     K->d_mgpart = nullptr;
 }
@@ -110,6 +113,25 @@ int aijhip::ksp_pc_vcycle(aijhip_ksp *K, const double *b, double *x, hipStream_t
 }
 
 namespace {
+
+// The multi-column V-cycle's level blocks and KSPMatSolve's work vectors for
+// the reserved width, so that a solve allocates nothing
+int reserve_mat_vcycle(aijhip_ksp *K) {
+    if (K->mat_vcycle <= 0 || K->cg.pc != AIJHIP_PC_GAMG) return AIJHIP_OK;
+    const int rc = aijhip::mg_multi_reserve(K->mgview, K->mat_vcycle, K->mgm);
+    return rc ? rc : cgm_reserve(K->cg, K->mm, K->mat_vcycle);
+}
+
+// A diagonal PC on an m x k block of either layout: Z = D^-1 R (PCApply_Jacobi's
+// product) or, dinv NULL, Z = R (PC none); one lane per entry
+__global__ __launch_bounds__(kVecThreads) void k_pc_diag(int64_t m, int32_t k, int il, const double *__restrict__ dinv,
+                                                         const double *R, int64_t ldr, double *Z, int64_t ldz) {
+    GRID_STRIDE(t, m * k) {
+        const int64_t i = il ? t / k : t % m, j = il ? t % k : t / m;
+        const double r = R[il ? i * ldr + j : i + j * ldr];
+        Z[il ? i * ldz + j : i + j * ldz] = dinv ? dinv[i] * r : r;
+    }
+}
 
 // What the single-GPU handle plugs into the CG driver.
 struct KspOperator final : CGOperator {
@@ -368,6 +390,7 @@ int aijhip_ksp_set_up(aijhip_ksp_t K) {
     ksp_free(K);
     int rc = cg_set_up(K->cg, *A, true);
     if (!rc && K->cg.pc == AIJHIP_PC_GAMG) rc = gamg_setup(K);
+    if (!rc) rc = reserve_mat_vcycle(K);
     if (rc) {
         ksp_free(K);
         return rc;
@@ -589,6 +612,21 @@ bool blocks_overlap(bool il, int64_t m, int64_t k, const double *B, int64_t ldb,
     return b0 < xe && x0 < be;
 }
 
+const char *const kNoWidth =
+    "KSPMatSolve serves PC none and Jacobi: the V-cycle has no multi-column "
+    "form (solve the columns one by one with aijhip_ksp_solve)";
+
+// Whether the handle's PC has a multi-column form at width k: none and Jacobi
+// always, GAMG within the reserved width (aijhip_ksp_set_mat_vcycle_width)
+int mat_width_check(aijhip_ksp_t K, int32_t k) {
+    if (K->cg.pc == AIJHIP_PC_NONE || K->cg.pc == AIJHIP_PC_JACOBI) return AIJHIP_OK;
+    if (K->cg.pc != AIJHIP_PC_GAMG || K->mat_vcycle == 0) return cg_fail(AIJHIP_ERR_STATE, kNoWidth);
+    if (k > K->mat_vcycle)
+        return cg_fail(AIJHIP_ERR_STATE, "k = " + std::to_string(k) + " is above the reserved V-cycle width " +
+                                             std::to_string(K->mat_vcycle) + " (aijhip_ksp_set_mat_vcycle_width)");
+    return AIJHIP_OK;
+}
+
 // KSPMatSolve's argument checks, all before any device work. *go = 0: nothing to do (k = 0).
 int mat_solve_check(aijhip_ksp_t K, int32_t k, int layout, const double *B, int64_t ldb, const double *X, int64_t ldx,
                     int *go) {
@@ -605,9 +643,7 @@ int mat_solve_check(aijhip_ksp_t K, int32_t k, int layout, const double *B, int6
     if (ldx < minld) return cg_fail(AIJHIP_ERR_ARG, "ldx " + std::to_string(ldx) + " is below " + std::to_string(minld));
     if (m > 0 && (!B || !X)) return cg_fail(AIJHIP_ERR_ARG, "NULL dense array");
     if (blocks_overlap(il, m, k, B, ldb, X, ldx)) return cg_fail(AIJHIP_ERR_ARG, "B and X overlap");
-    if (K->cg.pc != AIJHIP_PC_NONE && K->cg.pc != AIJHIP_PC_JACOBI)
-        return cg_fail(AIJHIP_ERR_STATE, "KSPMatSolve serves PC none and Jacobi: the V-cycle has no multi-column "
-                                         "form (solve the columns one by one with aijhip_ksp_solve)");
+    if (const int rc = mat_width_check(K, k)) return rc;
     *go = 1;
     return AIJHIP_OK;
 }
@@ -628,7 +664,77 @@ int aijhip_ksp_mat_solve(aijhip_ksp_t K, int32_t k, int layout, const double *B,
     DeviceGuard g(K->A->device);
     K->cg.poll = 8;
     if (const char *v = std::getenv("AIJHIP_KSP_POLL")) K->cg.poll = std::max(1, std::atoi(v));
-    return cgm_solve(K->cg, K->mm, *K->A, k, layout, B, ldb, X, ldx, reinterpret_cast<hipStream_t>(stream));
+    const CGMultiPC mg{&K->mgview, &K->mgm};
+    return cgm_solve(K->cg, K->mm, *K->A, k, layout, B, ldb, X, ldx, reinterpret_cast<hipStream_t>(stream),
+                     K->cg.pc == AIJHIP_PC_GAMG ? &mg : nullptr);
+}
+
+int aijhip_ksp_set_mat_vcycle_width(aijhip_ksp_t K, int32_t kmax) {
+    if (kmax < 0 || kmax > AIJHIP_KSP_MAX_RHS)
+        return cg_fail(AIJHIP_ERR_ARG,
+                       "kmax = " + std::to_string(kmax) + " is outside 0.." + std::to_string(AIJHIP_KSP_MAX_RHS));
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    K->mat_vcycle = kmax;
+    if (!K->set_up || K->a_gen != K->A->plan_gen || K->v_gen != K->A->values_gen) return AIJHIP_OK;
+    DeviceGuard g(K->A->device);  // a set-up handle: the blocks now, the hierarchy as it is
+    return reserve_mat_vcycle(K);
+}
+
+int aijhip_ksp_get_mat_vcycle_width(aijhip_ksp_t K, int32_t *kmax) {
+    if (!K || !kmax) return cg_fail(AIJHIP_ERR_ARG, "NULL argument");
+    *kmax = K->mat_vcycle;
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_pc_apply(aijhip_ksp_t K, const double *r, double *z, void *stream) {
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    const int64_t m = K->A->m;
+    if (m > 0 && (!r || !z)) return cg_fail(AIJHIP_ERR_ARG, "NULL vector");
+    if (m > 0 && r == z) return cg_fail(AIJHIP_ERR_ARG, "r and z alias");
+    const int rc = aijhip_ksp_set_up(K);
+    if (rc || m == 0) return rc;
+    DeviceGuard g(K->A->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (K->cg.pc == AIJHIP_PC_GAMG) return aijhip::ksp_pc_vcycle(K, r, z, s, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(k_pc_diag, dim3(K->cg.vec_grid), dim3(kVecThreads), 0, s, m, 1, 1,
+                       K->cg.pc == AIJHIP_PC_JACOBI ? K->cg.d_dinv : nullptr, r, (int64_t)1, z, (int64_t)1);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? AIJHIP_OK : cg_hip(e, "PCApply");
+}
+
+int aijhip_ksp_pc_mat_apply(aijhip_ksp_t K, int32_t k, int layout, const double *R, int64_t ldr, double *Z,
+                            int64_t ldz, void *stream) {
+    int go = 0;
+    int rc = mat_solve_check(K, k, layout, R, ldr, Z, ldz, &go);
+    if (rc || !go) return rc;
+    if ((rc = aijhip_ksp_set_up(K))) return rc;
+    const int64_t m = K->A->m;
+    if (m == 0) return AIJHIP_OK;
+    DeviceGuard g(K->A->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool il = layout == AIJHIP_DENSE_INTERLEAVED;
+    if (K->cg.pc != AIJHIP_PC_GAMG) {
+        const int64_t n = m * k;
+        const dim3 grid((unsigned)std::max<int64_t>(
+            1, std::min<int64_t>((n + kVecThreads - 1) / kVecThreads, (int64_t)K->A->n_cu * 8)));
+        hipLaunchKernelGGL(k_pc_diag, grid, dim3(kVecThreads), 0, s, m, k, il ? 1 : 0,
+                           K->cg.pc == AIJHIP_PC_JACOBI ? K->cg.d_dinv : nullptr, R, ldr, Z, ldz);
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? AIJHIP_OK : cg_hip(e, "PCMatApply");
+    }
+    // the V-cycle runs on tight interleaved blocks: others go through the
+    // handle's finest staging blocks
+    const double *rt = R;
+    double *zt = Z;
+    if (!il || ldr != k) {
+        cgm_copy_block(m, k, K->A->n_cu, R, ldr, il, K->mgm.lev[0].b, k, true, s);
+        rt = K->mgm.lev[0].b;
+    }
+    if (!il || ldz != k) zt = K->mgm.lev[0].x;
+    if ((rc = aijhip::mg_vcycle_multi(K->mgview, K->mgm, k, rt, zt, s, nullptr))) return rc;
+    if (zt != Z) cgm_copy_block(m, k, K->A->n_cu, zt, k, true, Z, ldz, il, s);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? AIJHIP_OK : cg_hip(e, "PCMatApply");
 }
 
 int aijhip_ksp_mat_solve_host(aijhip_ksp_t K, int32_t k, int layout, const double *B, int64_t ldb, double *X,
@@ -697,11 +803,48 @@ int aijhip_ksp_get_mat_solve_bytes(aijhip_ksp_t K, int32_t k, int64_t *bytes, in
     if (!bytes) return cg_fail(AIJHIP_ERR_ARG, "NULL argument");
     if (k < 0 || k > AIJHIP_KSP_MAX_RHS) return cg_fail(AIJHIP_ERR_ARG, "k is outside 0..AIJHIP_KSP_MAX_RHS");
     if (!K->set_up) return cg_fail(AIJHIP_ERR_STATE, "KSP is not set up");
-    if (K->cg.pc != AIJHIP_PC_NONE && K->cg.pc != AIJHIP_PC_JACOBI)
+    if (K->cg.pc != AIJHIP_PC_NONE && K->cg.pc != AIJHIP_PC_JACOBI && (K->cg.pc != AIJHIP_PC_GAMG || K->mat_vcycle == 0))
         return cg_fail(AIJHIP_ERR_STATE, "KSPMatSolve serves PC none and Jacobi: the V-cycle has no multi-column form");
-    int64_t sp = 0;
-    const int rc = aijhip_mat_mat_mult_get_plan(K->A, k, AIJHIP_DENSE_INTERLEAVED, nullptr, nullptr, &sp);
+    int rc = mat_width_check(K, k);
     if (rc) return rc;
+    int64_t sp = 0;
+    rc = aijhip_mat_mat_mult_get_plan(K->A, k, AIJHIP_DENSE_INTERLEAVED, nullptr, nullptr, &sp);
+    if (rc) return rc;
+    if (K->cg.pc == AIJHIP_PC_GAMG) {
+        // CG: km_aypx 40 m k, km_dot 16 m k, km_update 24 m k (reads R, W;
+        // writes R), km_dots 16 m k (reads Z, R). The V-cycle, per smoothed
+        // level of m_l rows: every product at its MatMatMult bytes (A_l 2 its
+        // times for Richardson(its), 2 its + 2 for Chebyshev(its), P and P^T
+        // once), the start x = f D^-1 b 16 m_l k + 8 m_l (reads b, D^-1; writes
+        // x), and the epilogues' row operands beyond a product's own X and Y:
+        // residual 8 m_l k (b), interpolation 8 m_l k (x), a Richardson step
+        // 8 m_l k + 8 m_l chunks (b, D^-1), a Chebyshev step with p_km1
+        // 16 m_l k + 8 m_l chunks; the coarse solve 16 m_c k + 8 m_c.
+        const int64_t m = K->A->m, ch = mat_solve_chunks(k);
+        int64_t vec = 96 * m * k;
+        const int nl = (int)K->mg.size();
+        for (int l = 0; l < nl; ++l) {
+            const MGLevel &L = K->mg[l];
+            const int64_t ml = L.m;
+            vec += 16 * ml * k + 8 * ml;
+            if (l == nl - 1) break;
+            const bool cheby = L.smooth == AIJHIP_MG_SMOOTH_CHEBYSHEV;
+            const int64_t its = L.its;
+            const int64_t n_rich = cheby ? 1 : 2 * its - 1;   // steps of the Richardson form (Chebyshev's start going up)
+            const int64_t n_cheb = cheby ? 2 * its : 0;       // Chebyshev steps; the first going down has no p_km1
+            const int64_t n_pm1 = cheby ? 2 * its - 1 : 0;
+            int64_t la = 0, lp = 0, lt = 0;
+            if ((rc = aijhip_mat_mat_mult_get_plan(L.A, k, AIJHIP_DENSE_INTERLEAVED, nullptr, nullptr, &la)) ||
+                (rc = aijhip_mat_mat_mult_get_plan(L.P, k, AIJHIP_DENSE_INTERLEAVED, nullptr, nullptr, &lp)) ||
+                (rc = aijhip_mat_mat_mult_get_plan(L.P->transpose, k, AIJHIP_DENSE_INTERLEAVED, nullptr, nullptr, &lt)))
+                return rc;
+            sp += (n_rich + n_cheb + 1) * la + lp + lt;
+            vec += 8 * ml * k + 8 * ml * k + (n_rich + n_cheb) * (8 * ml * k + 8 * ml * ch) + n_pm1 * 8 * ml * k;
+        }
+        *bytes = sp + vec;
+        if (spmm_bytes) *spmm_bytes = sp;
+        return AIJHIP_OK;
+    }
     // km_aypx 40 m k (reads Z, P, X; writes P, X), km_dot 16 m k (reads P, W),
     // km_update 32 m k (reads R, W; writes R, Z) and, Jacobi, D^-1 once per chunk
     const int64_t m = K->A->m;

@@ -57,4 +57,31 @@ bool mg_smoother_needs_w(const MGLevelView &L);
 int mg_vcycle(const std::vector<MGLevelView> &lv, const double *b0, double *x0, hipStream_t s, const int *stop,
               double *dots = nullptr, bool *dots_done = nullptr);
 
+// The multi-column V-cycle's level blocks: b, x, r and w of every level, m_l x
+// cap_k interleaved (a cycle of k <= cap_k columns uses leading dimension k).
+// Level 0's b and x are staging for callers whose blocks are not tight
+// interleaved. Owned by the handle (aijhip_ksp_set_mat_vcycle_width).
+struct MGMultiBlocks {
+    struct Level {
+        double *b = nullptr, *x = nullptr, *r = nullptr, *w = nullptr;
+    };
+    int32_t cap_k = 0;
+    std::vector<Level> lev;
+};
+int mg_multi_reserve(const std::vector<MGLevelView> &lv, int32_t kmax, MGMultiBlocks &mb);
+void mg_multi_free(MGMultiBlocks &mb);
+
+// PCMatApply_MG on one GPU (op, Ao, Po NULL on every level): one V-cycle on
+// the k columns of the tight interleaved m x k blocks B0 -> X0 (leading
+// dimension k), column j entry for entry mg_vcycle on column j: the same
+// smoothers, zero-guess starts and coarse solve, every smoothing step and
+// residual one launch_spmm with its epilogue on every level (no unfused form;
+// AIJHIP_MG_UNFUSED does not reach it), restriction launch_spmm(plain) on
+// Pd->transpose, interpolation launch_spmm(add) on Pd. Going down the steps
+// rotate x and w, coming up x and r, from a first buffer chosen by the parity
+// of the step count, so the result lands in X0 without a copy and a step's
+// result never aliases the operand it gathers.
+int mg_vcycle_multi(const std::vector<MGLevelView> &lv, const MGMultiBlocks &mb, int32_t k, const double *B0,
+                    double *X0, hipStream_t s, const int *stop);
+
 }  // namespace aijhip

@@ -27,6 +27,10 @@
 //
 // Every halo_post is followed by exactly one halo_finish or halo_abort on
 // every return path (mpi_internal.h).
+//
+// mg_vcycle_multi is the same cycle on k columns at once (single GPU, m_l x k
+// interleaved level blocks): the same expressions per entry, every product one
+// launch_spmm over all columns with the step in its epilogue (mg_cycle.h).
 #include "mg_cycle.h"
 
 #include <algorithm>
@@ -107,6 +111,30 @@ __global__ __launch_bounds__(256) void k_offdiag_axpy(int32_t nr, const int32_t 
         double sum = 0.0;
         for (int32_t k = rai[q]; k < rai[q + 1]; ++k) sum += aa[k] * g[aj[k]];
         y[o] = y[o] + (scale ? f * scale[o] : 1.0) * (-sum);
+    }
+}
+
+// The multi-column V-cycle's vector pass over an m x k interleaved level block
+// (leading dimension k): x = f (D^-1 b) with dinv[i / k] — the zero-guess
+// start of either smoother and the coarse solve (f = 1.0 multiplies to the bits
+// of k_jacobi's literal form). V2 (k even): n counts pairs, 16-byte accesses.
+template <bool V2>
+__global__ __launch_bounds__(kVecThreads) void k_jacobi_multi(int64_t n, int32_t k, const double *__restrict__ dinv,
+                                                              const double *__restrict__ b, double *x, double f,
+                                                              const int *stop) {
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
+    if (stop && *stop) return;
+    GRID_STRIDE(i, n) {
+        if constexpr (V2) {
+            const double di = dinv[2 * i / k];
+            const f64x2 bv = reinterpret_cast<const f64x2 *>(b)[i];
+            f64x2 xv;
+            xv.x = f * (di * bv.x);
+            xv.y = f * (di * bv.y);
+            reinterpret_cast<f64x2 *>(x)[i] = xv;
+        } else {
+            x[i] = f * (dinv[i / k] * b[i]);
+        }
     }
 }
 
@@ -370,6 +398,130 @@ int mg_vcycle(const std::vector<MGLevelView> &lv, const double *b0, double *x0, 
             std::swap(cur, oth);
         }
         if (dp && dots_done) *dots_done = true;
+    }
+    e = hipGetLastError();
+    return e == hipSuccess ? AIJHIP_OK : gerr(e, "kernel launch");
+}
+
+void mg_multi_free(MGMultiBlocks &mb) {
+    for (MGMultiBlocks::Level &L : mb.lev) {
+        hipFree(L.b); hipFree(L.x); hipFree(L.r); hipFree(L.w);
+    }
+    mb.lev.clear();
+    mb.cap_k = 0;
+}
+
+int mg_multi_reserve(const std::vector<MGLevelView> &lv, int32_t kmax, MGMultiBlocks &mb) {
+    if (kmax <= mb.cap_k && mb.lev.size() == lv.size()) return AIJHIP_OK;
+    mg_multi_free(mb);
+    mb.lev.assign(lv.size(), MGMultiBlocks::Level());
+    for (size_t l = 0; l < lv.size(); ++l) {
+        const size_t vb = sizeof(double) * (size_t)std::max<int32_t>(lv[l].m, 1) * (size_t)kmax;
+        MGMultiBlocks::Level &L = mb.lev[l];
+        hipError_t e;
+        if ((e = hipMalloc(&L.b, vb)) != hipSuccess || (e = hipMalloc(&L.x, vb)) != hipSuccess ||
+            (e = hipMalloc(&L.r, vb)) != hipSuccess || (e = hipMalloc(&L.w, vb)) != hipSuccess) {
+            mg_multi_free(mb);
+            return gerr(e, "multi-column level blocks");
+        }
+    }
+    mb.cap_k = kmax;
+    return AIJHIP_OK;
+}
+
+int mg_vcycle_multi(const std::vector<MGLevelView> &lv, const MGMultiBlocks &mb, int32_t k, const double *B0,
+                    double *X0, hipStream_t s, const int *stop) {
+    const int nl = (int)lv.size();
+    if (k < 1 || k > mb.cap_k || (int)mb.lev.size() != nl || nl < 1)
+        return gerr(hipErrorInvalidValue, "multi-column level blocks not reserved for this width");
+    for (const MGLevelView &L : lv)
+        if (L.op || L.Ao || L.Po) return gerr(hipErrorInvalidValue, "the multi-column V-cycle is single-GPU");
+    const int64_t ld = k;
+    const int il = AIJHIP_DENSE_INTERLEAVED;
+    auto B = [&](int l) { return l == 0 ? B0 : (const double *)mb.lev[l].b; };
+    auto X = [&](int l) { return l == 0 ? X0 : mb.lev[l].x; };
+    // x = f (D^-1 b) over the level's m_l k entries
+    auto jacobi = [&](const MGLevelView &L, int l, double f, double *x) {
+        // pairs only where every 16-byte access is aligned (level 0's blocks are the caller's)
+        const bool v2 = (k & 1) == 0 &&
+                        ((reinterpret_cast<uintptr_t>(B(l)) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
+        const int64_t n = (int64_t)L.m * k / (v2 ? 2 : 1);
+        const dim3 g((unsigned)std::max<int64_t>(
+            1, std::min<int64_t>((n + kVecThreads - 1) / kVecThreads, (int64_t)L.Ad->n_cu * 8)));
+        if (v2) hipLaunchKernelGGL(k_jacobi_multi<true>, g, dim3(kVecThreads), 0, s, n, k, L.dinv, B(l), x, f, stop);
+        else hipLaunchKernelGGL(k_jacobi_multi<false>, g, dim3(kVecThreads), 0, s, n, k, L.dinv, B(l), x, f, stop);
+    };
+    // One smoothing step from pk, one product of A_l with its epilogue:
+    // Richardson out = pk + c2 D^-1 (b - A pk), or Chebyshev out = (c0 pm1 +
+    // c1 pk) + c2 D^-1 (b - A pk) (pm1 NULL: no c0 term). out != pk.
+    auto step = [&](const MGLevelView &L, int l, bool cheby, const double *pm1, const double *pk, double *out,
+                    double c0, double c1, double c2) -> int {
+        SpmmOp op;
+        op.op = cheby ? kSpmmCheby : kSpmmPost;
+        op.B = B(l);
+        op.PM1 = pm1;
+        op.dinv = L.dinv;
+        op.c0 = c0; op.c1 = c1; op.c2 = c2;
+        const hipError_t e1 = launch_spmm(*L.Ad, k, il, pk, ld, out, ld, s, op, stop);
+        return e1 == hipSuccess ? AIJHIP_OK : gerr(e1, "multi-column smoothing");
+    };
+    int rc;
+    hipError_t e;
+    for (int l = 0; l < nl; ++l) {
+        const MGLevelView &L = lv[l];
+        if (l == nl - 1) {  // coarse: preonly + Jacobi
+            jacobi(L, l, 1.0, X(l));
+            break;
+        }
+        // smoothd from a zero guess, rotating x and w so that the last step lands in x
+        const bool cheby = L.smooth == AIJHIP_MG_SMOOTH_CHEBYSHEV;
+        const int n = cheby ? L.its : L.its - 1;
+        double *w = mb.lev[l].w, *r = mb.lev[l].r;
+        double *cur = n % 2 == 0 ? X(l) : w, *oth = n % 2 == 0 ? w : X(l);
+        jacobi(L, l, cheby ? L.scale : L.rscale, cur);
+        for (int i = 0; i < n; ++i) {
+            if (cheby)
+                rc = step(L, l, true, i == 0 ? nullptr : oth, cur, oth, 1.0 - L.omega[i], L.omega[i],
+                          L.omega[i] * L.scale);
+            else
+                rc = step(L, l, false, nullptr, cur, oth, 0.0, 0.0, L.rscale);
+            if (rc) return rc;
+            std::swap(cur, oth);
+        }
+        SpmmOp res;  // r = b - A x
+        res.op = kSpmmResid;
+        res.B = B(l);
+        if ((e = launch_spmm(*L.Ad, k, il, X(l), ld, r, ld, s, res, stop)) != hipSuccess)
+            return gerr(e, "multi-column residual");
+        // MatRestrict: b_{l+1} = P^T r
+        if ((e = launch_spmm(*L.Pd->transpose, k, il, r, ld, mb.lev[l + 1].b, ld, s, SpmmOp(), stop)) != hipSuccess)
+            return gerr(e, "multi-column restriction");
+    }
+    for (int l = nl - 2; l >= 0; --l) {
+        const MGLevelView &L = lv[l];
+        // MatInterpolateAdd t = x + P x_c into x or r by the step count's
+        // parity, then smoothu from t rotating x and r (mg_vcycle's fused form)
+        const bool cheby = L.smooth == AIJHIP_MG_SMOOTH_CHEBYSHEV;
+        const int n = cheby ? L.its + 1 : L.its;
+        double *alt = mb.lev[l].r;
+        double *cur = n % 2 == 0 ? X(l) : alt, *oth = n % 2 == 0 ? alt : X(l);
+        SpmmOp add;
+        add.op = kSpmmAdd;
+        add.B = X(l);
+        if ((e = launch_spmm(*L.Pd, k, il, X(l + 1), ld, cur, ld, s, add, stop)) != hipSuccess)
+            return gerr(e, "multi-column interpolation");
+        for (int i = 0; i < n; ++i) {
+            if (!cheby) {
+                rc = step(L, l, false, nullptr, cur, oth, 0.0, 0.0, L.rscale);
+            } else if (i == 0) {
+                rc = step(L, l, false, nullptr, cur, oth, 0.0, 0.0, L.scale);
+            } else {  // p_kp1 over p_km1 (cur holds p_k, oth p_km1)
+                const double om = L.omega[i - 1];
+                rc = step(L, l, true, oth, cur, oth, 1.0 - om, om, om * L.scale);
+            }
+            if (rc) return rc;
+            std::swap(cur, oth);
+        }
     }
     e = hipGetLastError();
     return e == hipSuccess ? AIJHIP_OK : gerr(e, "kernel launch");

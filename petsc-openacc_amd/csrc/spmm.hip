@@ -24,6 +24,11 @@
 // read the same LDS words and their gathers are W contiguous doubles. Column
 // X: j = t / nrows, row = t % nrows — a wave's lanes walk down one column.
 // All index arithmetic into X and Y is 64-bit.
+//
+// A launch may carry an epilogue (SpmmOp, aijhip_internal.h: MatMultAdd and the
+// V-cycle's residual, Richardson and Chebyshev steps on interleaved blocks,
+// the Ep* functors below) and a device stop flag past which every workgroup
+// returns at once; without either it is EpPlain<false>, the launch as it was.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -89,19 +94,175 @@ __device__ __forceinline__ void task_of(int t, int nrows, int &row, int &jg) {
     }
 }
 
+// What a launch does with a (row, column group)'s sums: the smoothing
+// epilogues of the multi-column V-cycle (mg_vcycle_multi), the single-vector
+// Ops of aijhip_kernels.hip (OpMult<true>, OpMgResid, OpMgPost, OpMgCheby) with
+// the same expressions, parenthesised as there and nothing contracted. `row`
+// loads the lane's row operands before the sum (B, PM1 and the result laid out
+// as Y: `off` is the element's offset in Y; xo points at X(r, j), the gathered
+// operand's own entry on a square operator), `seed` starts the sum, `put`
+// stores and issues no load. Every workgroup returns at once past a set stop
+// flag. STOP = false is the launch as it was: no flag is read.
+template <bool STOP>
+struct EpPlain {
+    const int *stop;
+    template <int P>
+    struct Row {};
+    __device__ bool stopped() const {
+        if constexpr (STOP) return *stop != 0;
+        else return false;
+    }
+    template <int P>
+    __device__ void row(Row<P> &, const double *, int64_t, int64_t) const {}
+    template <int P>
+    __device__ void seed(double (&s)[P], const Row<P> &) const {
+#pragma unroll
+        for (int q = 0; q < P; ++q) s[q] = 0.0;
+    }
+    template <int P>
+    __device__ void put(double *y, const double (&s)[P], const Row<P> &) const {
+        st_cols<P>(y, s);
+    }
+};
+
+// Y = Z + A X, MatMultAdd's order: the sum starts from Z(o, j) and the
+// products are added to it in storage order (k_spmv_scalar's and the STREAM
+// kernels' one-lane rows: sum = op.seed(o), then += in order). Z may be Y.
+struct EpAdd {
+    const int *stop;
+    const double *Z;
+    template <int P>
+    struct Row {
+        double z[P];
+    };
+    __device__ bool stopped() const { return stop && *stop != 0; }
+    template <int P>
+    __device__ void row(Row<P> &w, const double *, int64_t, int64_t off) const {
+        ld_cols<P>(Z + off, w.z);
+    }
+    template <int P>
+    __device__ void seed(double (&s)[P], const Row<P> &w) const {
+#pragma unroll
+        for (int q = 0; q < P; ++q) s[q] = w.z[q];
+    }
+    template <int P>
+    __device__ void put(double *y, const double (&s)[P], const Row<P> &) const {
+        st_cols<P>(y, s);
+    }
+};
+
+// R = B + (-1) (A X) (OpMgResid)
+struct EpResid {
+    const int *stop;
+    const double *B;
+    template <int P>
+    struct Row {
+        double b[P];
+    };
+    __device__ bool stopped() const { return stop && *stop != 0; }
+    template <int P>
+    __device__ void row(Row<P> &w, const double *, int64_t, int64_t off) const {
+        ld_cols<P>(B + off, w.b);
+    }
+    template <int P>
+    __device__ void seed(double (&s)[P], const Row<P> &) const {
+#pragma unroll
+        for (int q = 0; q < P; ++q) s[q] = 0.0;
+    }
+    template <int P>
+    __device__ void put(double *y, const double (&s)[P], const Row<P> &w) const {
+        double v[P];
+#pragma unroll
+        for (int q = 0; q < P; ++q) v[q] = w.b[q] + (-1.0) * s[q];
+        st_cols<P>(y, v);
+    }
+};
+
+// X = T + sc (dinv_o (B + (-1) (A T))) (OpMgPost; sc = 1.0 multiplies to the
+// bits of the literal form). The gathered operand is T; the result is not T.
+struct EpPost {
+    const int *stop;
+    const double *B, *dinv;
+    double sc;
+    template <int P>
+    struct Row {
+        double t[P], b[P], di;
+    };
+    __device__ bool stopped() const { return stop && *stop != 0; }
+    template <int P>
+    __device__ void row(Row<P> &w, const double *xo, int64_t r, int64_t off) const {
+        ld_cols<P>(xo, w.t);
+        ld_cols<P>(B + off, w.b);
+        w.di = dinv[r];
+    }
+    template <int P>
+    __device__ void seed(double (&s)[P], const Row<P> &) const {
+#pragma unroll
+        for (int q = 0; q < P; ++q) s[q] = 0.0;
+    }
+    template <int P>
+    __device__ void put(double *y, const double (&s)[P], const Row<P> &w) const {
+        double v[P];
+#pragma unroll
+        for (int q = 0; q < P; ++q) v[q] = w.t[q] + sc * (w.di * (w.b[q] + (-1.0) * s[q]));
+        st_cols<P>(y, v);
+    }
+};
+
+// OUT = (c0 PM1 + c1 PK) + c2 (dinv_o (B + (-1) (A PK))), without PM1
+// (NULL) c1 PK + that (OpMgCheby, both forms). The gathered operand is PK; OUT
+// may be PM1's storage (a lane reads its own PM1 entries before it writes them),
+// never PK's.
+struct EpCheby {
+    const int *stop;
+    const double *B, *PM1, *dinv;
+    double c0, c1, c2;
+    template <int P>
+    struct Row {
+        double m[P], k[P], b[P], di;
+    };
+    __device__ bool stopped() const { return stop && *stop != 0; }
+    template <int P>
+    __device__ void row(Row<P> &w, const double *xo, int64_t r, int64_t off) const {
+        if (PM1) ld_cols<P>(PM1 + off, w.m);
+        ld_cols<P>(xo, w.k);
+        ld_cols<P>(B + off, w.b);
+        w.di = dinv[r];
+    }
+    template <int P>
+    __device__ void seed(double (&s)[P], const Row<P> &) const {
+#pragma unroll
+        for (int q = 0; q < P; ++q) s[q] = 0.0;
+    }
+    template <int P>
+    __device__ void put(double *y, const double (&s)[P], const Row<P> &w) const {
+        double v[P];
+#pragma unroll
+        for (int q = 0; q < P; ++q) {
+            const double corr = c2 * (w.di * (w.b[q] + (-1.0) * s[q]));
+            v[q] = PM1 ? (c0 * w.m[q] + c1 * w.k[q]) + corr : c1 * w.k[q] + corr;
+        }
+        st_cols<P>(y, v);
+    }
+};
+
 // Path 0: one lane per (row, column) over all m rows (compressed rows, long
 // rows, SCALAR / VECTOR plans, the 16-wave geometries). An empty row gives +0.0.
-template <bool IL>
+template <bool IL, class E>
 __global__ __launch_bounds__(256) void k_spmm_generic(int32_t m, int w, const int32_t *__restrict__ ai,
                                                       const int32_t *__restrict__ aj, const double *__restrict__ aa,
-                                                      Dense<IL> D) {
+                                                      Dense<IL> D, E ep) {
+    if (ep.stopped()) return;
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (int64_t)m * w) return;
     const int64_t row = IL ? t / w : t % m, j = IL ? t % w : t / m;
     const int64_t k1 = ai[row + 1];
-    double s = 0.0;
-    for (int64_t k = ai[row]; k < k1; ++k) s += aa[k] * *D.xp(aj[k], j);
-    *D.yp(row, j) = s;
+    typename E::template Row<1> rw{};
+    ep.template row<1>(rw, D.xp(row, j), row, D.yp(row, j) - D.Y);
+    double s[1];
+    ep.template seed<1>(s, rw);
+    for (int64_t k = ai[row]; k < k1; ++k) s[0] += aa[k] * *D.xp(aj[k], j);
+    ep.template put<1>(D.yp(row, j), s, rw);
 }
 
 // Path 1: one workgroup per row block. Phase 1 stages aj and aa of the block's
@@ -109,15 +270,16 @@ __global__ __launch_bounds__(256) void k_spmm_generic(int32_t m, int w, const in
 // value pairs from an even start (the arrays' 2-entry tail pad keeps the last
 // pair in bounds). Phase 2: the tasks sum from LDS in storage order, the loads
 // of eight entries issued ahead of their dependent adds.
-template <int W, bool IL, int P>
+template <int W, bool IL, int P, class E>
 __global__ __launch_bounds__(kSpmmThreads) void k_spmm_csr(const BlockDesc *__restrict__ blk,
                                                            const int32_t *__restrict__ ai,
                                                            const int32_t *__restrict__ aj,
-                                                           const double *__restrict__ aa, Dense<IL> D) {
+                                                           const double *__restrict__ aa, Dense<IL> D, E ep) {
     static_assert(W % P == 0 && (P == 1 || IL), "the pair variant owns two adjacent interleaved columns");
     constexpr int T = kSpmmThreads, G = W / P;
     __shared__ double sa[kSpmmCap];
     __shared__ int32_t sj[kSpmmCap];
+    if (ep.stopped()) return;
     const BlockDesc d = blk[blockIdx.x];
     if (d.nk < 0) return;
     const int t = threadIdx.x;
@@ -143,7 +305,10 @@ __global__ __launch_bounds__(kSpmmThreads) void k_spmm_csr(const BlockDesc *__re
         const int32_t rs = ai[r], n = ai[r + 1] - rs;
         const int32_t *cj = sj + (rs - d.k0);
         const double *ca = sa + (rs - d.k0);
-        double s[P] = {};
+        typename E::template Row<P> rw{};
+        ep.template row<P>(rw, D.xp(r, j), r, D.yp(r, j) - D.Y);
+        double s[P];
+        ep.template seed<P>(s, rw);
         for (int32_t e0 = 0; e0 < n; e0 += 8) {
             double xv[8][P];
 #pragma unroll
@@ -157,7 +322,7 @@ __global__ __launch_bounds__(kSpmmThreads) void k_spmm_csr(const BlockDesc *__re
                     for (int q = 0; q < P; ++q) s[q] += a * xv[e][q];
                 }
         }
-        st_cols<P>(D.yp(r, j), s);
+        ep.template put<P>(D.yp(r, j), s, rw);
     }
 }
 
@@ -168,17 +333,18 @@ __global__ __launch_bounds__(kSpmmThreads) void k_spmm_csr(const BlockDesc *__re
 // and the next blocks' descriptors are loaded while the current tasks gather.
 // A task past the block's tasks has a row of length 0: it gathers nothing and
 // does not store.
-template <int W, bool IL, int P>
+template <int W, bool IL, int P, class E>
 __global__ __launch_bounds__(kSpmmTmplThreads) void k_spmm_template(const BlockDesc *__restrict__ blk, int nblk,
                                                                     const uint8_t *__restrict__ pid,
                                                                     const int32_t *__restrict__ ptab,
                                                                     const double *__restrict__ pval, int ntab,
-                                                                    int npat, Dense<IL> D) {
+                                                                    int npat, Dense<IL> D, E ep) {
     static_assert(W % P == 0 && (P == 1 || IL), "the pair variant owns two adjacent interleaved columns");
     constexpr int T = kSpmmTmplThreads, U = kSpmmTmplTasks, G = W / P;
     constexpr int TPT = (kPatTableMax + T - 1) / T;
     __shared__ int32_t tab[kPatTableMax];
     __shared__ double val[kPatTableMax];
+    if (ep.stopped()) return;
     const int t = threadIdx.x, NG = (int)gridDim.x, g = (int)blockIdx.x;
     int first = g, step = NG, last = nblk;
     if (NG >= 8 && (NG & 7) == 0) {
@@ -221,7 +387,8 @@ __global__ __launch_bounds__(kSpmmTmplThreads) void k_spmm_template(const BlockD
                 }
                 int st[U], n[U], nmax = 0;
                 int64_t r[U], j[U];
-                double s[U][P] = {};
+                double s[U][P];
+                typename E::template Row<P> rw[U] = {};
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const bool own = base + t + u * T < ntask;
@@ -231,6 +398,8 @@ __global__ __launch_bounds__(kSpmmTmplThreads) void k_spmm_template(const BlockD
                     nmax = max(nmax, n[u]);
                     r[u] = (int64_t)d.row0 + row[u];
                     j[u] = (int64_t)jg[u] * P;
+                    if (own) ep.template row<P>(rw[u], D.xp(r[u], j[u]), r[u], D.yp(r[u], j[u]) - D.Y);
+                    ep.template seed<P>(s[u], rw[u]);
                 }
                 for (int32_t e0 = 0; e0 < nmax; e0 += 8) {
                     double xv[U][8][P];
@@ -251,7 +420,7 @@ __global__ __launch_bounds__(kSpmmTmplThreads) void k_spmm_template(const BlockD
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    if (base + t + u * T < ntask) st_cols<P>(D.yp(r[u], j[u]), s[u]);
+                    if (base + t + u * T < ntask) ep.template put<P>(D.yp(r[u], j[u]), s[u], rw[u]);
                     row[u] = rown[u];
                     jg[u] = jgn[u];
                     p[u] = pn[u];
@@ -277,45 +446,65 @@ bool pair_wanted() {
     return !(v && *v) || std::atoi(v) != 0;
 }
 
-template <int W, bool IL, int P>
-hipError_t launch_chunk(const aijhip_mat &A, int path, const Dense<IL> &D, hipStream_t s) {
+template <int W, bool IL, int P, class E>
+hipError_t launch_chunk(const aijhip_mat &A, int path, const Dense<IL> &D, const E &ep, hipStream_t s) {
     const Plan &Pl = A.plan;
     if (path == kSpmmTemplate) {
         int g = (int)std::min<int64_t>(Pl.n_blocks, (int64_t)A.n_cu * kSpmmTmplWgPerCu);
         if (g >= 8) g &= ~7;
-        hipLaunchKernelGGL((k_spmm_template<W, IL, P>), dim3(g), dim3(kSpmmTmplThreads), 0, s, Pl.d_blocks, Pl.n_blocks,
-                           Pl.d_pid, Pl.d_ptab, Pl.d_pval, Pl.n_ptab, Pl.n_pat, D);
+        hipLaunchKernelGGL((k_spmm_template<W, IL, P, E>), dim3(g), dim3(kSpmmTmplThreads), 0, s, Pl.d_blocks,
+                           Pl.n_blocks, Pl.d_pid, Pl.d_ptab, Pl.d_pval, Pl.n_ptab, Pl.n_pat, D, ep);
     } else {
-        hipLaunchKernelGGL((k_spmm_csr<W, IL, P>), dim3(Pl.n_blocks), dim3(kSpmmThreads), 0, s, Pl.d_blocks, A.d_ai,
-                           A.d_aj, A.d_aa, D);
+        hipLaunchKernelGGL((k_spmm_csr<W, IL, P, E>), dim3(Pl.n_blocks), dim3(kSpmmThreads), 0, s, Pl.d_blocks, A.d_ai,
+                           A.d_aj, A.d_aa, D, ep);
     }
     return hipGetLastError();
 }
 
-template <int W, bool IL>
-hipError_t launch_width(const aijhip_mat &A, int path, const Dense<IL> &D, hipStream_t s) {
+// rowops: the epilogue's row operands (laid out as Y), which the pair variant
+// reads with 16-byte loads too
+template <int W, bool IL, class E>
+hipError_t launch_width(const aijhip_mat &A, int path, const Dense<IL> &D, const E &ep, uintptr_t rowops,
+                        hipStream_t s) {
     if (path == kSpmmGeneric) {
         const int64_t tasks = (int64_t)A.m * W;
-        hipLaunchKernelGGL((k_spmm_generic<IL>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, s, A.m, W, A.d_ai,
-                           A.d_aj, A.d_aa, D);
+        hipLaunchKernelGGL((k_spmm_generic<IL, E>), dim3((unsigned)((tasks + 255) / 256)), dim3(256), 0, s, A.m, W,
+                           A.d_ai, A.d_aj, A.d_aa, D, ep);
         return hipGetLastError();
     }
     if (A.plan.n_blocks == 0) return hipSuccess;
     if constexpr (IL && W >= 2) {
-        const bool aligned = ((reinterpret_cast<uintptr_t>(D.X) | reinterpret_cast<uintptr_t>(D.Y)) & 15) == 0 &&
-                             ((D.ldx | D.ldy) & 1) == 0;
-        if (aligned && pair_wanted()) return launch_chunk<W, IL, 2>(A, path, D, s);
+        const bool aligned =
+            ((reinterpret_cast<uintptr_t>(D.X) | reinterpret_cast<uintptr_t>(D.Y) | rowops) & 15) == 0 &&
+            ((D.ldx | D.ldy) & 1) == 0;
+        if (aligned && pair_wanted()) return launch_chunk<W, IL, 2, E>(A, path, D, ep, s);
     }
-    return launch_chunk<W, IL, 1>(A, path, D, s);
+    return launch_chunk<W, IL, 1, E>(A, path, D, ep, s);
 }
 
-template <bool IL>
-hipError_t launch_layout(const aijhip_mat &A, int path, int w, const Dense<IL> &D, hipStream_t s) {
+template <bool IL, class E>
+hipError_t launch_layout(const aijhip_mat &A, int path, int w, const Dense<IL> &D, const E &ep, uintptr_t rowops,
+                         hipStream_t s) {
     switch (w) {
-        case 8: return launch_width<8, IL>(A, path, D, s);
-        case 4: return launch_width<4, IL>(A, path, D, s);
-        case 2: return launch_width<2, IL>(A, path, D, s);
-        default: return launch_width<1, IL>(A, path, D, s);
+        case 8: return launch_width<8, IL, E>(A, path, D, ep, rowops, s);
+        case 4: return launch_width<4, IL, E>(A, path, D, ep, rowops, s);
+        case 2: return launch_width<2, IL, E>(A, path, D, ep, rowops, s);
+        default: return launch_width<1, IL, E>(A, path, D, ep, rowops, s);
+    }
+}
+
+// One chunk's epilogue: the row operands at the chunk's first column (yo, Y's offset)
+hipError_t launch_op(const aijhip_mat &A, int path, int w, const Dense<true> &D, const SpmmOp &op, int64_t yo,
+                     const int *stop, hipStream_t s) {
+    const double *B = op.B ? op.B + yo : nullptr, *M = op.PM1 ? op.PM1 + yo : nullptr;
+    const uintptr_t rowops = reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(M);
+    switch (op.op) {
+        case kSpmmAdd: return launch_layout<true>(A, path, w, D, EpAdd{stop, B}, rowops, s);
+        case kSpmmResid: return launch_layout<true>(A, path, w, D, EpResid{stop, B}, rowops, s);
+        case kSpmmPost: return launch_layout<true>(A, path, w, D, EpPost{stop, B, op.dinv, op.c2}, rowops, s);
+        case kSpmmCheby:
+            return launch_layout<true>(A, path, w, D, EpCheby{stop, B, M, op.dinv, op.c0, op.c1, op.c2}, rowops, s);
+        default: return hipErrorInvalidValue;
     }
 }
 
@@ -331,15 +520,28 @@ int spmm_path(const aijhip_mat &A) {
 }
 
 hipError_t launch_spmm(const aijhip_mat &A, int32_t k, int layout, const double *X, int64_t ldx, double *Y,
-                       int64_t ldy, hipStream_t s) {
+                       int64_t ldy, hipStream_t s, const SpmmOp &op, const int *stop) {
     if (A.m == 0) return hipSuccess;
     const int path = spmm_path(A);
     const bool il = layout == AIJHIP_DENSE_INTERLEAVED;
+    if (op.op != kSpmmPlain) {  // the epilogues: interleaved blocks, the operands they name present
+        const bool square = op.op == kSpmmPost || op.op == kSpmmCheby;
+        if (!il || !op.B || (square && (!op.dinv || A.m != A.n || X == Y))) return hipErrorInvalidValue;
+    }
     for (int32_t j0 = 0; j0 < k;) {
         const int w = spmm_chunk_width(k - j0);
         const int64_t xo = il ? (int64_t)j0 : (int64_t)j0 * ldx, yo = il ? (int64_t)j0 : (int64_t)j0 * ldy;
-        const hipError_t e = il ? launch_layout<true>(A, path, w, Dense<true>{X + xo, Y + yo, ldx, ldy}, s)
-                                : launch_layout<false>(A, path, w, Dense<false>{X + xo, Y + yo, ldx, ldy}, s);
+        hipError_t e;
+        if (op.op != kSpmmPlain)
+            e = launch_op(A, path, w, Dense<true>{X + xo, Y + yo, ldx, ldy}, op, yo, stop, s);
+        else if (stop)
+            e = il ? launch_layout<true>(A, path, w, Dense<true>{X + xo, Y + yo, ldx, ldy}, EpPlain<true>{stop}, 0, s)
+                   : launch_layout<false>(A, path, w, Dense<false>{X + xo, Y + yo, ldx, ldy}, EpPlain<true>{stop}, 0, s);
+        else
+            e = il ? launch_layout<true>(A, path, w, Dense<true>{X + xo, Y + yo, ldx, ldy}, EpPlain<false>{nullptr}, 0,
+                                         s)
+                   : launch_layout<false>(A, path, w, Dense<false>{X + xo, Y + yo, ldx, ldy}, EpPlain<false>{nullptr},
+                                          0, s);
         if (e != hipSuccess) return e;
         j0 += w;
     }

@@ -32,6 +32,8 @@ KSP_SYMBOLS = (
     "aijhip_ksp_solve_host", "aijhip_ksp_set_mg_smoother", "aijhip_ksp_get_mg_smoother",
     "aijhip_ksp_mat_solve", "aijhip_ksp_mat_solve_host", "aijhip_ksp_get_mat_solve_results",
     "aijhip_ksp_get_mat_solve_history", "aijhip_ksp_get_mat_solve_bytes",
+    "aijhip_ksp_set_mat_vcycle_width", "aijhip_ksp_get_mat_vcycle_width", "aijhip_ksp_pc_apply",
+    "aijhip_ksp_pc_mat_apply",
 )
 KSP_MAX_RHS = 64  # AIJHIP_KSP_MAX_RHS
 _P = ctypes.c_void_p
@@ -78,6 +80,10 @@ def _lib():
                                                        ctypes.POINTER(ctypes.c_int32)]
         L.aijhip_ksp_get_mat_solve_bytes.argtypes = [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
                                                      ctypes.POINTER(ctypes.c_int64)]
+        L.aijhip_ksp_set_mat_vcycle_width.argtypes = [_P, ctypes.c_int32]
+        L.aijhip_ksp_get_mat_vcycle_width.argtypes = [_P, ctypes.POINTER(ctypes.c_int32)]
+        L.aijhip_ksp_pc_apply.argtypes = [_P, _P, _P, _P]
+        L.aijhip_ksp_pc_mat_apply.argtypes = L.aijhip_ksp_mat_solve.argtypes
         _bound = True
     return L
 
@@ -86,10 +92,12 @@ class KSPCG:
     """KSPCG on a SeqAIJHIP operator (device vectors)."""
 
     def __init__(self, A, rtol=1e-5, atol=1e-50, dtol=1e5, max_it=10000, pc="jacobi",
-                 norm="preconditioned", guess_nonzero=False, gamg=None, smoother=None):
+                 norm="preconditioned", guess_nonzero=False, gamg=None, smoother=None, mat_vcycle=0):
         """gamg: aijhip_gamg_params_t fields; smoother: the GAMG level smoother,
         dict(type="richardson"|"chebyshev", its=, scale=, lo=, hi=) (gamg.mg_smoother;
-        None: Richardson(1), scale 1)."""
+        None: Richardson(1), scale 1); mat_vcycle: the widest block mat_solve and
+        pc_mat_apply take with pc="gamg" (aijhip_ksp_set_mat_vcycle_width; 0: they
+        refuse a GAMG handle)."""
         L = _lib()
         self.A = A
         self._h = _P()
@@ -106,6 +114,35 @@ class KSPCG:
             _pkg._check(L.aijhip_ksp_set_mg_smoother(self._h, ctypes.byref(self._sm)))
         _pkg._check(L.aijhip_ksp_set_norm_type(self._h, NORM_TYPES[norm]))
         _pkg._check(L.aijhip_ksp_set_initial_guess_nonzero(self._h, int(guess_nonzero)))
+        if mat_vcycle:
+            self.set_mat_vcycle_width(mat_vcycle)
+
+    def set_mat_vcycle_width(self, kmax: int):
+        """Reserve the multi-column V-cycle's level blocks for kmax columns (at
+        set-up, or at once on a set-up handle, whose hierarchy stays)."""
+        _pkg._check(_lib().aijhip_ksp_set_mat_vcycle_width(self._h, int(kmax)))
+
+    @property
+    def mat_vcycle_width(self) -> int:
+        v = ctypes.c_int32()
+        _pkg._check(_lib().aijhip_ksp_get_mat_vcycle_width(self._h, ctypes.byref(v)))
+        return v.value
+
+    def pc_apply(self, r, z, stream=None):
+        """PCApply (aijhip_ksp_pc_apply): z = M^-1 r for the handle's PC."""
+        _pkg._check(_lib().aijhip_ksp_pc_apply(self._h, _pkg._dev_ptr(r, self.A.m, "r"),
+                                               _pkg._dev_ptr(z, self.A.m, "z"), _pkg._stream_handle(stream)))
+
+    def pc_mat_apply(self, R, Z, stream=None):
+        """PCMatApply (aijhip_ksp_pc_mat_apply): Z = M^-1 R for float64 GPU
+        tensors of shape (m, k) in one layout, as mat_solve's B and X."""
+        import torch
+        for t, what in ((R, "R"), (Z, "Z")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_cuda:
+                raise TypeError(f"pc_mat_apply: {what} must be a float64 torch tensor on the GPU")
+        k, layout, ldr, ldz = self._mat_solve_layout(R.shape, R.stride(), Z.shape, Z.stride())
+        _pkg._check(_lib().aijhip_ksp_pc_mat_apply(self._h, k, layout, R.data_ptr(), ldr, Z.data_ptr(), ldz,
+                                                   _pkg._stream_handle(stream)))
 
     def set_tolerances(self, rtol, atol, dtol, max_it):
         _pkg._check(_lib().aijhip_ksp_set_tolerances(self._h, rtol, atol, dtol, int(max_it)))
@@ -144,7 +181,8 @@ class KSPCG:
     def mat_solve(self, B, X, stream=None):
         """KSPMatSolve (aijhip_ksp_mat_solve): A X = B for float64 GPU tensors
         of shape (m, k), k <= 64, the columns solved as independent CG
-        recurrences in lock step (PC none / Jacobi). Layout and leading
+        recurrences in lock step (PC none / Jacobi, and GAMG on a handle made with
+        mat_vcycle >= k: one multi-column V-cycle per iteration). Layout and leading
         dimensions come from the strides as in SeqAIJHIP.mat_mult; B and X take
         one layout. X is overwritten (read first with a nonzero initial guess)."""
         import torch

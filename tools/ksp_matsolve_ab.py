@@ -10,7 +10,12 @@ after round, by the wall clock around the synchronous calls. The single solves
 are the handle's own form (fused p.w, and on row templates Z not stored), so
 the ratio is what a caller gains or loses by switching calls. One JSON line.
 
-    python3 tools/ksp_matsolve_ab.py [--grid 300] [--max-it 200] [--rounds 3] [--ks 2 4 8] [--plans csr auto] [--out profiles/kspmat/ksp_matsolve_ab.json]
+--pc gamg: CG + GAMG instead (a handle with mat_vcycle = max k), solved to
+the reference's tolerances (rtol 1e-14, atol 1e-12) rather than for a fixed
+count: one mat_solve of the block against the k fused single solves of its
+columns; the output goes to profiles/kspmat/ksp_matsolve_gamg_ab.json.
+
+    python3 tools/ksp_matsolve_ab.py [--pc jacobi|gamg] [--grid 300] [--max-it 200] [--rounds 3] [--ks 2 4 8] [--plans csr auto] [--out profiles/kspmat/ksp_matsolve_ab.json]
 """
 from __future__ import annotations
 
@@ -44,8 +49,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--ks", type=int, nargs="+", default=[2, 4, 8])
     ap.add_argument("--plans", nargs="+", default=["csr", "auto"], choices=["csr", "auto"])
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "kspmat" / "ksp_matsolve_ab.json"))
+    ap.add_argument("--pc", default="jacobi", choices=["jacobi", "gamg"])
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    gamg = args.pc == "gamg"
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / "kspmat" / ("ksp_matsolve_gamg_ab.json" if gamg else "ksp_matsolve_ab.json"))
+    solver = dict(rtol=1e-14, atol=1e-12, max_it=10000, pc="gamg", mat_vcycle=max(args.ks)) if gamg else \
+        dict(rtol=0.0, atol=0.0, max_it=args.max_it, pc="jacobi")
     pkg = importlib.import_module("petsc-openacc_amd")
     K = importlib.import_module("petsc-openacc_amd.ksp")
     dev = torch.device("cuda:0")
@@ -59,7 +70,7 @@ def main():
         if plan == "csr":
             A.set_option("row_patterns", 0)
         m = A.m
-        with K.KSPCG(A, rtol=0.0, atol=0.0, max_it=args.max_it, pc="jacobi") as ksp:
+        with K.KSPCG(A, **solver) as ksp:
             ksp.set_up()
             info = A.info()
             print(f"ksp_matsolve_ab: {plan}: {info}", file=sys.stderr, flush=True)
@@ -98,17 +109,21 @@ def main():
                 t_k = statistics.median(times["k_solves"])
                 its = max(r[0] for r in res)
                 nbytes, spmm_bytes = ksp.mat_solve_bytes(k)
-                rec = {"grid": args.grid, "plan": plan, "spmm_path": path, "k": k, "max_it": args.max_it,
+                # the k solves' bytes: each column's own iteration count
+                k_its = sum(i for i, _ in single) / k
+                rec = {"grid": args.grid, "pc": args.pc, "plan": plan, "spmm_path": path, "k": k,
+                       "max_it": solver["max_it"],
                        "mat_solve_s": round(t_mat, 4), "k_solves_s": round(t_k, 4),
                        "mat_solve_s_all": [round(t, 4) for t in times["mat_solve"]],
                        "k_solves_s_all": [round(t, 4) for t in times["k_solves"]],
                        "ratio_to_k_solves": round(t_mat / t_k, 4),
                        "mat_solve_its_reason": sorted(set((r[0], r[1]) for r in res)),
                        "k_solves_its_reason": sorted(set(single)),
+                       "spmm_share_of_bytes": round(spmm_bytes / nbytes, 4),
                        "mat_solve_bytes_per_iter": nbytes, "spmm_bytes_per_iter": spmm_bytes,
                        "k_solves_bytes_per_iter": k * single_bytes, "single_fused": ksp.fused,
                        "mat_solve_frac_8TBs": round(nbytes * its / t_mat / HBM_BYTES_PER_S, 4),
-                       "k_solves_frac_8TBs": round(k * single_bytes * its / t_k / HBM_BYTES_PER_S, 4),
+                       "k_solves_frac_8TBs": round(k * single_bytes * k_its / t_k / HBM_BYTES_PER_S, 4),
                        "host_syncs": ksp.host_syncs}
                 print(f"ksp_matsolve_ab: {rec}", file=sys.stderr, flush=True)
                 cases.append(rec)
