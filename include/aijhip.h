@@ -295,6 +295,11 @@ int aijhip_mat_set_option(aijhip_mat_t A, int option, int value);
 /* New values, same nonzero structure (host aa[nz]): the re-upload half of
  * MatAssemblyEnd_SeqAIJ's hook (step2 MatAssemblyEnd patch:42-44). */
 int aijhip_mat_update_values(aijhip_mat_t A, const double *aa);
+/* The same from a device array d_aa[nz] (the update counterpart of
+ * aijhip_mat_create_from_device: no PCIe traffic). d_aa may be the handle's
+ * own values array (aijhip_mat_get_device_csr) rewritten in place: no copy is
+ * made then. */
+int aijhip_mat_update_values_device(aijhip_mat_t A, const double *d_aa);
 
 /* New structure and values (MAT_FINAL_ASSEMBLY after compaction): drops the
  * device copy and re-uploads everything (step2 MatAssemblyEnd patch:21-29,

@@ -148,6 +148,23 @@ int aijhip_gamg_diag_prolong(int32_t m, int32_t n, const int32_t *ti, const int3
  * agg[i] = -1). b_ones != 0: B is all 1.0 (the finest level's form). */
 int aijhip_gamg_diag_tentative(int32_t m, int32_t na, const int32_t *agg, const double *B, int32_t b_ones,
                                double *Bc, double *p0, double *s2);
+/* C = A B where C's pattern is known: ci (m + 1 offsets) and cj, ascending in
+ * every row and holding every column the product reaches (the pattern of
+ * aijhip_gamg_diag_rowprod on operands of the same structure; it may hold
+ * more). Only the values are computed, by the numeric-only kernel the GAMG
+ * refresh uses: each C(i, j) from +0.0, the products a_ik b_kj rounded and
+ * added in traversal order, a pattern column no product reaches left +0.0 —
+ * the bits of aijhip_gamg_diag_rowprod on the same operands. The rows go by
+ * their pattern length to a class of that capacity (aijhip_gamg_diag_get_passes:
+ * lanes, capacity, 1, capacity per launch); AIJHIP_ERR_STATE when a row holds
+ * 1024 columns or more (the refresh sends such a level to the host). */
+int aijhip_gamg_diag_rowprod_numeric(int32_t m, int32_t k, int32_t n, const int32_t *ai, const int32_t *aj,
+                                     const double *aa, const int32_t *bi, const int32_t *bj, const double *ba,
+                                     const int32_t *ci, const int32_t *cj, int32_t n_cu, aijhip_gamg_diag_t *out);
+/* Every (lanes per row, class capacity) pair the numeric-only kernel is
+ * instantiated for: pairs[2 q], pairs[2 q + 1], up to cap pairs; *n = their
+ * count. */
+int aijhip_gamg_diag_numeric_classes(int32_t *pairs, int32_t cap, int32_t *n);
 /* The result's rows, columns and entries; the hash-table launches recorded
  * (npasses); whether the register form of A P0 wrote the result. */
 int aijhip_gamg_diag_info(aijhip_gamg_diag_t h, int32_t *m, int32_t *n, int64_t *nz, int32_t *npasses,

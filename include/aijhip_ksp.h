@@ -156,6 +156,43 @@ int aijhip_ksp_get_pc_level(aijhip_ksp_t ksp, int32_t l, char which, int32_t *m,
 int aijhip_ksp_get_gamg_setup_path(aijhip_ksp_t ksp, int32_t cap, int32_t *path, int32_t *product_cols,
                                    int32_t *host_fallback);
 
+/* -pc_gamg_reuse_interpolation [ext] (default 0: every change of the operator
+ * takes the full set-up). With flg != 0, aijhip_ksp_set_up on a handle that is
+ * set up with AIJHIP_PC_GAMG, whose operator has the sparsity structure it was
+ * set up on (no aijhip_mat_assembly_end since) and new values or a new plan
+ * (aijhip_mat_update_values / _device, aijhip_mat_set_option), REFRESHES the
+ * hierarchy instead of rebuilding it. Kept: every P_l and P_l^T with their
+ * handles and plans, the sparsity pattern of every A_l, the level vectors, the
+ * multi-column blocks and the lock-step work vectors. Redone from the new
+ * values: A_(l+1) = P_l^T (A_l P_l) into the existing level operators (the
+ * numeric-only product: the sums in the set-up's order, the same bits as a
+ * full product of the same operands), the level handles' value copies and
+ * codes, D^-1 of every level, the fused-launch choices and the smoothers'
+ * scalars; for Chebyshev each level's emax(D^-1 A_l) is estimated again with
+ * the set-up's estimator, eig_its and eig_ksp. The prolongators keep the
+ * smoothing they were built with. The pattern of each A_l P_l is kept on the
+ * device between refreshes (made by the first refresh when the flag was set
+ * on a handle already set up). A level with a row of 1024 columns or more in
+ * A_l P_l or A_(l+1) is refreshed by the host builder's products on operands
+ * read back from the device. (AIJHIP_GAMG_REFRESH=host is a test and
+ * diagnostic switch: it sends every level of a handle there, for good on that
+ * handle, so that the host path runs on small operands; the same bits.) A new
+ * structure, PC type, GAMG parameters or
+ * smoother still take the full set-up; PC none and Jacobi ignore the flag. A
+ * refresh that fails leaves the handle not set up and returns the error; the
+ * next set-up is a full one. */
+int aijhip_ksp_set_gamg_reuse_interpolation(aijhip_ksp_t ksp, int flg);
+int aijhip_ksp_get_gamg_reuse_interpolation(aijhip_ksp_t ksp, int *flg);
+/* Set-ups this handle has run: full ones, refreshes, and the wall time of the
+ * last of either kind. Any out pointer may be NULL. */
+int aijhip_ksp_get_gamg_setup_counts(aijhip_ksp_t ksp, int32_t *full, int32_t *refreshed, double *last_seconds);
+/* Diagnostics: the device addresses of what aijhip_ksp_set_mat_vcycle_width
+ * reserves, for asserting that a call kept the allocations: per GAMG level
+ * the multi-column blocks b, x, r, w (4 per level, finest first), then
+ * KSPMatSolve's lock-step work vectors R, Z, P (0 where nothing is
+ * allocated). Up to cap entries are written; *n = their count (4 levels + 3). */
+int aijhip_ksp_get_mat_vcycle_reserve(aijhip_ksp_t ksp, int32_t cap, uint64_t *ptrs, int32_t *n);
+
 #define AIJHIP_KSP_MAX_RHS 64
 
 /* KSPMatSolve [ext]: A X = B, B and X m x k device blocks in one layout

@@ -47,7 +47,7 @@ DENSE_LAYOUTS = {"columns": 0, "interleaved": 1}
 ABI_SYMBOLS = (
     "aijhip_abi_version", "aijhip_last_error", "aijhip_device_count",
     "aijhip_mat_create", "aijhip_mat_create_from_device", "aijhip_mat_set_kernel", "aijhip_mat_set_option",
-    "aijhip_mat_update_values", "aijhip_mat_assembly_end", "aijhip_mat_mult",
+    "aijhip_mat_update_values", "aijhip_mat_update_values_device", "aijhip_mat_assembly_end", "aijhip_mat_mult",
     "aijhip_mat_mult_add", "aijhip_mat_mult_transpose", "aijhip_mat_mult_host",
     "aijhip_mat_mult_add_host", "aijhip_mat_mult_transpose_host",
     "aijhip_mat_get_info", "aijhip_mat_get_device_csr", "aijhip_mat_destroy",
@@ -132,6 +132,7 @@ def lib() -> ctypes.CDLL:
         L.aijhip_mat_set_kernel.argtypes = [_P, ctypes.c_int, ctypes.c_int]
         L.aijhip_mat_set_option.argtypes = [_P, ctypes.c_int, ctypes.c_int]
         L.aijhip_mat_update_values.argtypes = [_P, _P]
+        L.aijhip_mat_update_values_device.argtypes = [_P, _P]
         L.aijhip_mat_assembly_end.argtypes = [_P, ctypes.c_int64, _P, _P, _P]
         L.aijhip_mat_mult.argtypes = [_P, _P, _P, _P]
         L.aijhip_mat_mult_add.argtypes = [_P, _P, _P, _P, _P]
@@ -425,6 +426,11 @@ class SeqAIJHIP:
         if aa.shape[0] != self.nz:
             raise ValueError("update_values: nz mismatch")
         _check(lib().aijhip_mat_update_values(self._h, _np_ptr(aa, np.float64)))
+
+    def update_values_device(self, aa):
+        """update_values from a float64 GPU tensor of nz entries
+        (aijhip_mat_update_values_device: no host copy)."""
+        _check(lib().aijhip_mat_update_values_device(self._h, _dev_ptr(aa, self.nz, "aa")))
 
     def assembly_end(self, ai, aj, aa):
         ai = np.ascontiguousarray(ai, dtype=np.int32)

@@ -625,6 +625,7 @@ int structure_and_plan(aijhip_mat *A, const int32_t *ai, aijhip::HostVec<int32_t
     const int32_t m = A->m;
     const int64_t nz = A->nz;
     hipError_t e;
+    A->struct_gen = aijhip::next_plan_gen();  // a new sparsity structure
     // structure statistics (PETSc a->nonzerorowcnt, MatCheckCompressedRow);
     // row ranges on host threads for large operands, as the planning below
     int32_t nzrows = 0, maxlen = 0;
@@ -885,6 +886,27 @@ int attach_transpose(aijhip_mat *A, int32_t *tai, int32_t *taj, double *taa) {
     A->transpose = T;
     return AIJHIP_OK;
 }
+
+int values_changed(aijhip_mat *A) {
+    if (A->plan.d_sslot) {  // the gather-ordered copy of the values
+        const hipError_t e = aijhip::build_gather_order(*A, A->plan, true);
+        if (e != hipSuccess) return hipfail(e, "update values");
+    }
+    // templates / value codes hold the old values, and explicitly requested
+    // ones may fit the new values: plan again
+    if (A->plan.d_pval || A->plan.d_vcode || A->plan.d_svcode || A->requested_tune.vcodes > 0 ||
+        A->requested_tune.templates > 0) {
+        const int rc = plan_build(A);
+        if (rc) return rc;
+    }
+    A->values_gen = aijhip::next_plan_gen();  // a set-up KSP redoes its PC set-up
+    if (A->transpose) {  // A^T values are stale
+        free_matrix(A->transpose);
+        delete A->transpose;
+        A->transpose = nullptr;
+    }
+    return AIJHIP_OK;
+}
 }  // namespace aijhip
 
 namespace aijhip {
@@ -1044,23 +1066,21 @@ int aijhip_mat_update_values(aijhip_mat_t A, const double *aa) {
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess && A->nz > 0)
         e = hipMemcpy(A->d_aa, aa, sizeof(double) * (size_t)A->nz, hipMemcpyHostToDevice);
-    if (e == hipSuccess && A->plan.d_sslot)  // the gather-ordered copy of the values
-        e = aijhip::build_gather_order(*A, A->plan, true);
     if (e != hipSuccess) return hipfail(e, "update values");
-    // templates / value codes hold the old values, and explicitly requested
-    // ones may fit the new values: plan again
-    if (A->plan.d_pval || A->plan.d_vcode || A->plan.d_svcode || A->requested_tune.vcodes > 0 ||
-        A->requested_tune.templates > 0) {
-        rc = plan_build(A);
-        if (rc) return rc;
-    }
-    A->values_gen = aijhip::next_plan_gen();  // a set-up KSP redoes its PC set-up
-    if (A->transpose) {  // A^T values are stale
-        free_matrix(A->transpose);
-        delete A->transpose;
-        A->transpose = nullptr;
-    }
-    return AIJHIP_OK;
+    return aijhip::values_changed(A);
+}
+
+int aijhip_mat_update_values_device(aijhip_mat_t A, const double *d_aa) {
+    int rc = check_handle(A);
+    if (rc) return rc;
+    if (A->nz > 0 && !d_aa) return fail(AIJHIP_ERR_ARG, "d_aa is NULL");
+    DeviceGuard g(A->device);
+    if (g.err != hipSuccess) return hipfail(g.err, "set device");
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && A->nz > 0 && d_aa != A->d_aa)  // (the handle's own array: written in place)
+        e = hipMemcpy(A->d_aa, d_aa, sizeof(double) * (size_t)A->nz, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) return hipfail(e, "update values (device)");
+    return aijhip::values_changed(A);
 }
 
 int aijhip_mat_assembly_end(aijhip_mat_t A, int64_t nz, const int32_t *ai, const int32_t *aj,

@@ -295,6 +295,11 @@ struct aijhip_mat {
     // D^-1, the GAMG hierarchy) when it moved, as PETSc's PCSetUp does when
     // the operator's state changed
     uint64_t values_gen = 0;
+    // changes only when the sparsity structure is new (aijhip_mat_create*,
+    // aijhip_mat_assembly_end): a re-plan (options, update_values on templates
+    // or value codes) leaves it, so a GAMG KSP with reuse-interpolation tells
+    // new values on the same pattern from a new pattern
+    uint64_t struct_gen = 0;
     int n_cu = 256;  // compute units of the device
     int32_t m = 0, n = 0;
     int64_t nz = 0;
@@ -444,6 +449,12 @@ hipError_t gather_lines_per_entry(const aijhip_mat &A, double *out);
 // freed on failure.
 int adopt_device_csr(int device, int32_t m, int32_t n, int64_t nz, int32_t *d_ai, int32_t *d_aj, double *d_aa,
                      const aijhip_mat *like, aijhip_mat **out);
+// A->d_aa was rewritten in place on the device (aijhip_mat_update_values_device
+// with the handle's own array; the GAMG refresh's level operators): the
+// gather-ordered copy's values again, a re-plan where templates or value codes
+// hold values, values_gen advanced, the stale transpose dropped. The caller has
+// synchronised the device. Returns an AIJHIP_* code.
+int values_changed(aijhip_mat *A);
 // Install A^T (device arrays, adopted) as A's transpose handle.
 int attach_transpose(aijhip_mat *A, int32_t *tai, int32_t *taj, double *taa);
 // Number of device column indices outside [0, n) (synchronous).

@@ -50,6 +50,9 @@ struct DeviceLevel {
     // the widest accumulator class the Galerkin products building P and
     // A_{l+1} needed: 0 = wavefront form, else 32 / 64 / 128 / 256 LDS columns
     int product_cols = 0;
+    // build_device(keep_ap): the pattern of A P (ai, aj; no values), kept for
+    // the refresh's numeric-only products; the level's new owner releases it
+    DCsr ap;
 };
 
 // Device set-up: levels are built on the device while the level has at least
@@ -60,8 +63,9 @@ struct DeviceLevel {
 // accumulators): B is then that level's near-null space for build_host_nns.
 // *overflow is true when that hand-over happened at a level the device
 // would otherwise have built (a product row past every device class).
+// keep_ap: every level built keeps the pattern of its A P (DeviceLevel::ap).
 int build_device(aijhip_mat *A0, const aijhip_gamg_params_t &p, std::vector<DeviceLevel> &levels,
-                 std::vector<double> &B, bool *more, bool *overflow = nullptr);
+                 std::vector<double> &B, bool *more, bool *overflow = nullptr, bool keep_ap = false);
 
 void free_device_levels(std::vector<DeviceLevel> &levels);
 
@@ -90,6 +94,18 @@ int galerkin_level(const DCsr &Av, const DCsr &P, DCsr &PT, DCsr &Ac, int n_cu, 
 int make_level_handle(int device, DCsr &C, aijhip_mat **out);
 // C = A B, the row-traversal product (scipy csr_matmat order).
 int rowprod_device(const DCsr &A, const DCsr &B, DCsr &C, int n_cu, int *cols_used);
+// ca = the values of A B on the known pattern (ci; cj ascending per row), the
+// numeric-only product of the GAMG refresh: rowprod_device's sums in its
+// order, no pattern work. *classes (may be NULL): the row classes the pattern
+// has, < 0 = not counted yet (counted and stored). AIJHIP_ERR_STATE: a row of
+// 1024 columns or more.
+int rowprod_numeric_device(const DCsr &A, const DCsr &B, const int32_t *ci, const int32_t *cj, double *ca, int n_cu,
+                           int *classes);
+// A handle's device CSR as a non-owning view.
+DCsr csr_view(const aijhip_mat &A);
+// emax(D^-1 A) as the set-up estimates it (its steps; cg: CG's Lanczos
+// estimate, else the power iteration), synchronous. A: stream_mg_fusable.
+int emax_device(const aijhip_mat &A, const double *dinv, int its, bool cg, double *emax);
 // The tentative prolongator's values: Bc[a] = ||B over aggregate a||, p0[i] =
 // B[i] / Bc[agg[i]] (device arrays).
 hipError_t tentative_device(int32_t m, int32_t na, const int32_t *agg, const double *B, double *Bc, double *p0,

@@ -1121,6 +1121,197 @@ int rowprod(const DCsr &A, const DCsr &B, DCsr &C, int n_cu, int *cols_used) {
     }
 }
 
+// ------------------------------------------------ the numeric-only product
+//
+// C = A * B where C's pattern (ci, cj ascending per row) is already known: the
+// GAMG refresh's Galerkin products, whose patterns the set-up made. The
+// traversal is k_rowprod_hash's — G lanes per output row within one wavefront,
+// A_i's terms in chunks of G broadcast by shuffle, the lanes side by side over
+// B row k's entries, D steps' first loads in flight together — so every
+// C(i, j) is the same sum in the same order from +0.0: the same bits. What
+// the known pattern removes is the hash table: the row's cj is staged in LDS
+// and a product's accumulator is its column's rank there (a binary search),
+// so there are no key claims, no count pass, no compaction or ranking and no
+// allocation. The read-modify-write needs no atomics for the reason it needs
+// none above: a B row holds a column once, and one wavefront's LDS operations
+// complete in program order. A column the pattern does not hold is dropped
+// (never an access out of the row's slots); a pattern column no product
+// reaches stays +0.0.
+// Rows go by their pattern length n to the class with lo < n <= CAP.
+template <int G, int CAP, int NG>
+__global__ __launch_bounds__(G *NG) void k_rowprod_numeric(int32_t m, const int32_t *__restrict__ ai,
+                                                           const int32_t *__restrict__ aj,
+                                                           const double *__restrict__ aa,
+                                                           const int32_t *__restrict__ bi,
+                                                           const int32_t *__restrict__ bj,
+                                                           const double *__restrict__ ba,
+                                                           const int32_t *__restrict__ ci,
+                                                           const int32_t *__restrict__ cj, double *ca, int32_t lo) {
+    static_assert(G >= 1 && G <= 64 && 64 % G == 0, "a group lies within one wavefront");
+    static_assert(NG * CAP * 12 <= 65536, "LDS per workgroup");
+    constexpr int D = G < 4 ? G : 4;  // steps whose first entries are loaded together
+    __shared__ int32_t s_col[NG * CAP];
+    __shared__ double s_val[NG * CAP];
+    const int g = threadIdx.x / G, l = threadIdx.x % G;
+    const int gbase = (threadIdx.x & 63) - l;  // the group's first lane within the wavefront
+    int32_t *col = s_col + g * CAP;
+    double *val = s_val + g * CAP;
+    for (int64_t i = (int64_t)blockIdx.x * NG + g; i < m; i += (int64_t)gridDim.x * NG) {
+        const int32_t o = ci[i];
+        const int n = ci[i + 1] - o;
+        if (n <= lo || n > CAP) continue;  // another class's row, or an empty one (group-uniform)
+        for (int s = l; s < n; s += G) {
+            col[s] = cj[o + s];
+            val[s] = 0.0;
+        }
+        __builtin_amdgcn_wave_barrier();
+        auto add = [&](int32_t c, double p) {
+            int lo_r = 0, hi_r = n;  // the first rank whose column is not below c
+            while (lo_r < hi_r) {
+                const int mid = (lo_r + hi_r) >> 1;
+                if (col[mid] < c) lo_r = mid + 1;
+                else hi_r = mid;
+            }
+            if (lo_r < n && col[lo_r] == c) val[lo_r] += p;
+        };
+        const int32_t k1 = ai[i + 1];
+        for (int32_t kc = ai[i]; kc < k1; kc += G) {
+            int32_t q0 = 0, q1 = 0;
+            double a = 0.0;
+            if (kc + l < k1) {
+                const int32_t j = aj[kc + l];
+                a = aa[kc + l];
+                q0 = bi[j];
+                q1 = bi[j + 1];
+            }
+            const int nk = min(G, k1 - kc);
+            for (int t0 = 0; t0 < nk; t0 += D) {
+                int32_t pb0[D], pb1[D], pc[D];
+                double pa[D], pv[D];
+#pragma unroll
+                for (int u = 0; u < D; ++u) {
+                    const int src = gbase + (t0 + u < nk ? t0 + u : 0);
+                    pb0[u] = __shfl(q0, src, 64);
+                    pb1[u] = t0 + u < nk ? __shfl(q1, src, 64) : pb0[u];
+                    pa[u] = __shfl(a, src, 64);
+                    pc[u] = -1;
+                    pv[u] = 0.0;
+                    if (pb0[u] + l < pb1[u]) {
+                        pc[u] = bj[pb0[u] + l];
+                        pv[u] = ba[pb0[u] + l];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < D; ++u) {
+                    if (t0 + u >= nk) break;  // group-uniform
+                    if (pc[u] >= 0) add(pc[u], pa[u] * pv[u]);
+                    for (int32_t q = pb0[u] + l + G; q < pb1[u]; q += G) add(bj[q], pa[u] * ba[q]);
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+        }
+        for (int s = l; s < n; s += G) ca[o + s] = val[s];
+        __builtin_amdgcn_wave_barrier();  // the slots are staged again for the group's next row
+    }
+}
+
+// The row classes by pattern length: capacities, and per class the rows in it
+// (cls[kNumericClasses]: rows of 1024 columns or more, which no class takes).
+constexpr int kNumericClasses = 4;
+constexpr int kNumericCap[kNumericClasses] = {16, 64, 256, 1024};
+constexpr int kNumericMaxCols = 1023;  // the hash product's reach (its largest table's keys)
+
+__global__ void k_numeric_row_classes(int32_t m, const int32_t *__restrict__ ci, int32_t *cls) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    int c = -1;
+    if (i < m) {
+        const int32_t n = ci[i + 1] - ci[i];
+        if (n > kNumericMaxCols) c = kNumericClasses;
+        else if (n > 0) c = n <= 16 ? 0 : n <= 64 ? 1 : n <= 256 ? 2 : 3;  // kNumericCap
+    }
+    for (int k = 0; k <= kNumericClasses; ++k) {
+        const int cnt = __popcll(__ballot(c == k));
+        if (cnt && (threadIdx.x & 63) == 0) atomicAdd(&cls[k], cnt);
+    }
+}
+
+// lanes per row for class c given the preferred G: at most the capacity; at
+// least 16 for the largest class, whose groups would not fill a wavefront
+// within the LDS otherwise
+int numeric_lanes(int G, int c) {
+    if (G > kNumericCap[c]) G = kNumericCap[c];
+    if (kNumericCap[c] == 1024 && G < 16) G = 16;
+    return G;
+}
+
+// groups per workgroup: at most 256 lanes and 32 KiB of LDS counted at 16 B
+// per slot (12 are used), but at least one wavefront of groups. That floor
+// wins for the fewest lanes of the two wide classes: (4, 256) and (16, 1024)
+// take 48 KiB for a single wavefront and run at 1 wave per SIMD
+// (profiles/gamg_refresh/resources.txt) — speed only, and a rare pairing: B
+// rows of at most 4 (16) entries under C rows of more than 64 (256) columns
+template <int G, int CAP>
+constexpr int numeric_groups() {
+    return std::max(64 / G, std::min(256 / G, 32768 / (16 * CAP)));
+}
+
+#define AIJHIP_NUMERIC_PAIRS(X)                                                                             \
+    X(4, 16) X(8, 16) X(16, 16) X(4, 64) X(8, 64) X(16, 64) X(32, 64) X(64, 64) X(4, 256) X(8, 256) X(16, 256) \
+    X(32, 256) X(64, 256) X(16, 1024) X(32, 1024) X(64, 1024)
+
+hipError_t rowprod_numeric_class(int c, int G, const DCsr &A, const DCsr &B, const int32_t *ci, const int32_t *cj,
+                                 double *ca, int n_cu) {
+    const int cap = kNumericCap[c], lo = c > 0 ? kNumericCap[c - 1] : 0;
+    if (g_trace) g_trace->passes.push_back({G, cap, 1, cap});
+#define AIJHIP_NUMERIC(GG, CC)                                                                                \
+    if (G == GG && cap == CC) {                                                                               \
+        constexpr int NG = numeric_groups<GG, CC>();                                                          \
+        const unsigned grid = (unsigned)std::min<int64_t>(blocks_for(A.m, NG), (int64_t)n_cu * 32);           \
+        hipLaunchKernelGGL((k_rowprod_numeric<GG, CC, NG>), dim3(grid), dim3(GG * NG), 0, nullptr, A.m, A.ai, \
+                           A.aj, A.aa, B.ai, B.aj, B.aa, ci, cj, ca, lo);                                     \
+        return hipGetLastError();                                                                             \
+    }
+    AIJHIP_NUMERIC_PAIRS(AIJHIP_NUMERIC)
+#undef AIJHIP_NUMERIC
+    return hipErrorInvalidValue;
+}
+
+// ca = the values of A * B on the pattern (ci, cj). *classes: bit c set when
+// class c holds rows (< 0: not known yet; counted here and returned, so that a
+// kept pattern is counted once). AIJHIP_ERR_STATE: a row of 1024 columns or
+// more (the caller takes the product on the host).
+int rowprod_numeric(const DCsr &A, const DCsr &B, const int32_t *ci, const int32_t *cj, double *ca, int n_cu,
+                    int *classes) {
+    if (A.m == 0) return AIJHIP_OK;
+    hipError_t e;
+    int mask = classes ? *classes : -1;
+    if (mask < 0) {
+        int32_t *d_cls = nullptr, h_cls[kNumericClasses + 1] = {};
+        if ((e = dalloc(&d_cls, kNumericClasses + 1)) != hipSuccess) return herr(e, "numeric product classes");
+        e = hipMemset(d_cls, 0, sizeof(h_cls));
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_numeric_row_classes, dim3(blocks_for(A.m, 256)), dim3(256), 0, nullptr, A.m, ci, d_cls);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpy(h_cls, d_cls, sizeof(h_cls), hipMemcpyDeviceToHost);
+        hipFree(d_cls);
+        if (e != hipSuccess) return herr(e, "numeric product classes");
+        if (h_cls[kNumericClasses] > 0) return AIJHIP_ERR_STATE;
+        mask = 0;
+        for (int c = 0; c < kNumericClasses; ++c) mask |= (h_cls[c] > 0) << c;
+        if (classes) *classes = mask;
+    }
+    // G lanes per row: B's mean row length rounded up to a power of two (rowprod's choice)
+    const double b_row = B.m > 0 ? (double)B.nz / (double)B.m : 0.0;
+    int G = 4;
+    while (G < 64 && G < b_row) G <<= 1;
+    for (int c = 0; c < kNumericClasses; ++c)
+        if ((mask >> c & 1) &&
+            (e = rowprod_numeric_class(c, numeric_lanes(G, c), A, B, ci, cj, ca, n_cu)) != hipSuccess)
+            return herr(e, "numeric product");
+    return AIJHIP_OK;
+}
+
 // S directly from A (k_strong_direct_*): *ok = false, nothing allocated,
 // when A has an unsorted row or the strong pattern is not symmetric (the
 // caller then gathers S u S^T).
@@ -1639,6 +1830,7 @@ void free_device_levels(std::vector<DeviceLevel> &levels) {
     for (size_t l = 0; l < levels.size(); ++l) {
         if (l > 0) aijhip_mat_destroy(levels[l].A);
         aijhip_mat_destroy(levels[l].P);
+        levels[l].ap.release();
     }
     levels.clear();
 }
@@ -2010,6 +2202,24 @@ int rowprod_device(const DCsr &A, const DCsr &B, DCsr &C, int n_cu, int *cols_us
     return rowprod(A, B, C, n_cu, cols_used);
 }
 
+int rowprod_numeric_device(const DCsr &A, const DCsr &B, const int32_t *ci, const int32_t *cj, double *ca, int n_cu,
+                           int *classes) {
+    return rowprod_numeric(A, B, ci, cj, ca, n_cu, classes);
+}
+
+DCsr csr_view(const aijhip_mat &A) { return view_of(A); }
+
+int emax_device(const aijhip_mat &A, const double *dinv, int its, bool cg, double *emax) {
+    hipError_t e = hipDeviceSynchronize();  // D^-1 is written on the null stream, the job runs on its own
+    if (e != hipSuccess) return herr(e, "emax estimate");
+    EmaxJob job;
+    job.start(A, dinv, its, cg, nullptr);
+    job.join();
+    if (job.e != hipSuccess) return herr(job.e, "emax estimate");
+    *emax = job.emax;
+    return AIJHIP_OK;
+}
+
 hipError_t tentative_device(int32_t m, int32_t na, const int32_t *agg, const double *B, double *Bc, double *p0,
                             bool b_ones) {
     return tentative(m, na, agg, B, Bc, p0, b_ones);
@@ -2050,7 +2260,7 @@ int prolong_from_T(const DCsr &T, const int32_t *d_agg, const double *d_p0, cons
 }
 
 int build_device(aijhip_mat *A0, const aijhip_gamg_params_t &p, std::vector<DeviceLevel> &levels,
-                 std::vector<double> &B, bool *more, bool *overflow) {
+                 std::vector<double> &B, bool *more, bool *overflow, bool keep_ap) {
     levels.clear();
     *more = false;
     if (overflow) *overflow = false;
@@ -2123,7 +2333,7 @@ int build_device(aijhip_mat *A0, const aijhip_gamg_params_t &p, std::vector<Devi
         lap("emax");
         int cols_used = 0;
         const DCsr Av = view_of(A);
-        DCsr P, PT, Ac;
+        DCsr P, PT, Ac, AP;
         double *d_p0 = nullptr, *d_Bc = nullptr;
         aijhip_mat *Ph = nullptr, *Ach = nullptr;
         // ---- tentative + smoothed prolongator
@@ -2131,8 +2341,10 @@ int build_device(aijhip_mat *A0, const aijhip_gamg_params_t &p, std::vector<Devi
                           &cols_used, levels.size() == 1);
         lap("prolongator");
         // ---- Galerkin operator A_c = P^T (A P)
-        if (!rc) rc = galerkin_level(Av, P, PT, Ac, n_cu, &cols_used, nullptr);
+        if (!rc) rc = galerkin_level(Av, P, PT, Ac, n_cu, &cols_used, keep_ap ? &AP : nullptr);
         lap("P^T*(AP)");
+        hipFree(AP.aa);  // (keep_ap: the pattern of A P stays with the level, its values do not)
+        AP.aa = nullptr;
         // ---- handles: P (with P^T attached for MatRestrict) and A_c
         if (!rc && !in_line) {
             jobs.emplace_back(new HandleJob());
@@ -2150,6 +2362,8 @@ int build_device(aijhip_mat *A0, const aijhip_gamg_params_t &p, std::vector<Devi
             levels.back().P = Ph;
             levels.back().emax = emax;
             levels.back().product_cols = cols_used;
+            levels.back().ap = AP;
+            AP = DCsr();
             Ph = nullptr;
             levels.push_back(DeviceLevel{Ach, nullptr, 0.0});
             Ach = nullptr;
@@ -2157,7 +2371,7 @@ int build_device(aijhip_mat *A0, const aijhip_gamg_params_t &p, std::vector<Devi
             lap("handles");
         }
         hipFree(dinv); hipFree(d_agg); hipFree(d_p0); hipFree(d_Bc);
-        P.release(); PT.release(); Ac.release();
+        P.release(); PT.release(); Ac.release(); AP.release();
         if (Ph) aijhip_mat_destroy(Ph);
         if (Ach) aijhip_mat_destroy(Ach);
         if (rc == AIJHIP_ERR_STATE) {  // a row past the device accumulators
@@ -2313,6 +2527,70 @@ int aijhip_gamg_diag_rowprod(int32_t m, int32_t k, int32_t n, const int32_t *ai,
     C.release();
     if (rc) return rc;
     *out = h.release();
+    return AIJHIP_OK;
+}
+
+int aijhip_gamg_diag_rowprod_numeric(int32_t m, int32_t k, int32_t n, const int32_t *ai, const int32_t *aj,
+                                     const double *aa, const int32_t *bi, const int32_t *bj, const double *ba,
+                                     const int32_t *ci, const int32_t *cj, int32_t n_cu, aijhip_gamg_diag_t *out) {
+    if (!out) return dfail(AIJHIP_ERR_ARG, "NULL out");
+    *out = nullptr;
+    if (!host_csr_ok(m, k, ai, aj, aa) || !host_csr_ok(k, n, bi, bj, ba)) return dfail(AIJHIP_ERR_ARG, "malformed CSR");
+    // the pattern: offsets from 0, columns in [0, n) ascending in every row
+    if (!ci || ci[0] != 0) return dfail(AIJHIP_ERR_ARG, "malformed pattern");
+    for (int32_t i = 0; i < m; ++i)
+        if (ci[i + 1] < ci[i]) return dfail(AIJHIP_ERR_ARG, "malformed pattern");
+    const int32_t cnz = ci[m];
+    if (cnz > 0 && !cj) return dfail(AIJHIP_ERR_ARG, "malformed pattern");
+    for (int32_t i = 0; i < m; ++i)
+        for (int32_t q = ci[i]; q < ci[i + 1]; ++q)
+            if (cj[q] < 0 || cj[q] >= n || (q > ci[i] && cj[q] <= cj[q - 1]))
+                return dfail(AIJHIP_ERR_ARG, "the pattern's columns must ascend within [0, n) in every row");
+    int rc = diag_device(&n_cu);
+    if (rc) return rc;
+    DCsr A, B, C;
+    hipError_t e;
+    C.m = m;
+    C.n = n;
+    C.nz = cnz;
+    if ((e = upload_csr(m, k, ai, aj, aa, A)) != hipSuccess || (e = upload_csr(k, n, bi, bj, ba, B)) != hipSuccess ||
+        (e = upload(&C.ai, ci, (int64_t)m + 1)) != hipSuccess || (e = upload(&C.aj, cj, (int64_t)cnz, 2)) != hipSuccess ||
+        (e = dalloc(&C.aa, (int64_t)cnz + 2)) != hipSuccess ||
+        // (the values start as NaN bits: an entry the kernel did not write shows)
+        (e = hipMemset(C.aa, 0xFF, sizeof(double) * ((size_t)cnz + 2))) != hipSuccess) {
+        A.release();
+        B.release();
+        C.release();
+        return herr(e, "upload");
+    }
+    std::unique_ptr<aijhip_gamg_diag> h(new aijhip_gamg_diag());
+    {
+        TraceScope ts(&h->trace);
+        rc = rowprod_numeric(A, B, C.ai, C.aj, C.aa, n_cu, nullptr);
+    }
+    if (rc == AIJHIP_ERR_STATE) dfail(rc, "a pattern row has more columns than the largest class holds");
+    if (!rc) rc = download_csr(C, h.get());
+    A.release();
+    B.release();
+    C.release();
+    if (rc) return rc;
+    *out = h.release();
+    return AIJHIP_OK;
+}
+
+int aijhip_gamg_diag_numeric_classes(int32_t *pairs, int32_t cap, int32_t *n) {
+    if (!n || (cap > 0 && !pairs)) return dfail(AIJHIP_ERR_ARG, "NULL argument");
+    static const int32_t all[][2] = {
+#define AIJHIP_NUMERIC(GG, CC) {GG, CC},
+        AIJHIP_NUMERIC_PAIRS(AIJHIP_NUMERIC)
+#undef AIJHIP_NUMERIC
+    };
+    const int32_t count = (int32_t)(sizeof(all) / sizeof(all[0]));
+    for (int32_t q = 0; q < std::min(cap, count); ++q) {
+        pairs[2 * q] = all[q][0];
+        pairs[2 * q + 1] = all[q][1];
+    }
+    *n = count;
     return AIJHIP_OK;
 }
 

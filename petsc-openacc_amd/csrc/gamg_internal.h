@@ -67,4 +67,16 @@ double lanczos_emax(const std::vector<double> &alpha, const std::vector<double> 
 int build_host_nns(int32_t m, const int32_t *ai, const int32_t *aj, const double *aa, const double *B,
                    const aijhip_gamg_params_t &p, aijhip_gamg_host_t *out, int32_t level0 = 0);
 
+
+// The GAMG refresh's host side (gamg_setup.cpp), on operands read back from
+// the level handles: the host builder's own routines, so the same order and
+// the same bits as a level the set-up built on the host.
+// A_c = P^T (A P) by the builder's spgemm / transpose; A m x m, P m x nc.
+int galerkin_host(int32_t m, const int32_t *ai, const int32_t *aj, const double *aa, int32_t nc, const int32_t *pi,
+                  const int32_t *pj, const double *pa, int threads, std::vector<int32_t> &ci,
+                  std::vector<int32_t> &cj, std::vector<double> &ca);
+// emax(D^-1 A) by the builder's estimate (eig_ksp 1: CG's Lanczos, else the
+// power iteration), D^-1 formed as the builder forms it.
+double emax_host(int32_t m, const int32_t *ai, const int32_t *aj, const double *aa, int its, int eig_ksp, int threads);
+
 }  // namespace aijhip_gamg

@@ -632,6 +632,37 @@ int aijhip_gamg_build_host(int32_t m, const int32_t *ai, const int32_t *aj, cons
 
 }  // extern "C"
 
+int aijhip_gamg::galerkin_host(int32_t m, const int32_t *ai, const int32_t *aj, const double *aa, int32_t nc,
+                               const int32_t *pi, const int32_t *pj, const double *pa, int threads,
+                               std::vector<int32_t> &ci, std::vector<int32_t> &cj, std::vector<double> &ca) {
+    try {
+        const int nt = nthreads(threads);
+        const View A{m, m, ai, aj, aa}, P{m, nc, pi, pj, pa};
+        CSR AP, PT, Ac;
+        spgemm(A, P, AP, nt);
+        transpose(P, PT, nt);
+        spgemm(view(PT), view(AP), Ac, nt);
+        ci.swap(Ac.ai);
+        cj.swap(Ac.aj);
+        ca.swap(Ac.aa);
+    } catch (const std::bad_alloc &) {
+        return AIJHIP_ERR_ALLOC;
+    } catch (const std::exception &) {
+        return AIJHIP_ERR_ARG;
+    }
+    return AIJHIP_OK;
+}
+
+double aijhip_gamg::emax_host(int32_t m, const int32_t *ai, const int32_t *aj, const double *aa, int its, int eig_ksp,
+                              int threads) {
+    const int nt = nthreads(threads);
+    const View A{m, m, ai, aj, aa};
+    const std::vector<double> d = diagonal(A, nt);
+    std::vector<double> dinv((size_t)m);
+    for (int32_t i = 0; i < m; ++i) dinv[i] = 1.0 / (d[i] == 0.0 ? 1.0 : d[i]);
+    return eig_ksp == 1 ? estimate_emax_cg(A, dinv, its, nt) : estimate_emax(A, dinv, its, nt);
+}
+
 int aijhip_gamg::build_host_nns(int32_t m, const int32_t *ai, const int32_t *aj, const double *aa, const double *B0,
                                 const aijhip_gamg_params_t &p, aijhip_gamg_host_t *out, int32_t level0) {
     if (!out || m < 0 || !ai || (ai[m] > 0 && (!aj || !aa))) return AIJHIP_ERR_ARG;

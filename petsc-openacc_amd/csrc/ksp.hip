@@ -70,6 +70,19 @@ struct aijhip_ksp {
     // how each level's coarsening was built (aijhip_ksp_get_gamg_setup_path)
     std::vector<int32_t> setup_path, setup_cols;
     bool setup_overflow = false;
+    // -pc_gamg_reuse_interpolation (aijhip_ksp_set_gamg_reuse_interpolation):
+    // new values on the structure the handle was set up on (s_gen: the
+    // operator's structure generation then) refresh the hierarchy (gamg_refresh)
+    bool reuse_interp = false;
+    uint64_t s_gen = 0;
+    int32_t n_full = 0, n_refreshed = 0;  // set-ups run (aijhip_ksp_get_gamg_setup_counts)
+    // per level with a P: the pattern of A_l P_l (ai, aj; no values) kept
+    // between refreshes, the row classes of it and of A_(l+1) (-1: not
+    // counted yet), and whether the level's products go to the host builder
+    // (a row past the numeric kernel's classes)
+    std::vector<aijhip_gamg::DCsr> ap;
+    std::vector<int> ap_cls, ac_cls;
+    std::vector<char> host_level;
 };
 
 namespace {
@@ -82,6 +95,11 @@ void mg_free(aijhip_ksp *K) {
     }
     K->mg.clear();
     K->mgview.clear();
+    for (aijhip_gamg::DCsr &p : K->ap) p.release();
+    K->ap.clear();
+    K->ap_cls.clear();
+    K->ac_cls.clear();
+    K->host_level.clear();
     aijhip::mg_multi_free(K->mgm);
     hipFree(K->d_mgpart);
     K->d_mgpart = nullptr;
@@ -177,7 +195,7 @@ int gamg_setup(aijhip_ksp *K) {
     std::vector<aijhip_gamg::DeviceLevel> dl;
     std::vector<double> B;
     bool more = false, overflow = false;
-    rc = aijhip_gamg::build_device(A, K->gamg, dl, B, &more, &overflow);
+    rc = aijhip_gamg::build_device(A, K->gamg, dl, B, &more, &overflow, K->reuse_interp);
     if (rc) return rc;
     K->setup_path.clear();
     K->setup_cols.clear();
@@ -219,6 +237,15 @@ int gamg_setup(aijhip_ksp *K) {
         K->setup_cols.push_back(-1);
     }
     K->mg.assign((size_t)nl, MGLevel());
+    K->ap.assign((size_t)nl - 1, aijhip_gamg::DCsr());
+    K->ap_cls.assign((size_t)nl - 1, -1);
+    K->ac_cls.assign((size_t)nl - 1, -1);
+    K->host_level.assign((size_t)nl - 1, 0);
+    for (int32_t l = 0; l < nd; ++l) {  // (reuse-interpolation: the device levels' A P patterns)
+        if (l + 1 < nl) K->ap[l] = dl[l].ap;
+        else dl[l].ap.release();
+        dl[l].ap = aijhip_gamg::DCsr();
+    }
     std::vector<double> lambda((size_t)nl, 0.0);  // each level's emax(D^-1 A) estimate (none on the coarsest)
     for (int32_t hl = 0; hl + 1 < nh; ++hl)
         aijhip_gamg_host_level_info(H, hl, nullptr, nullptr, nullptr, &lambda[nd - 1 + hl]);
@@ -294,6 +321,190 @@ int gamg_setup(aijhip_ksp *K) {
     }
     if ((e = hipDeviceSynchronize()) != hipSuccess) return cg_hip(e, "GAMG set-up");
     lap("level vectors, P^T");
+    return AIJHIP_OK;
+}
+
+// A device CSR's arrays on the host (the refresh's host side)
+struct HostCsr {
+    std::vector<int32_t> ai, aj;
+    std::vector<double> aa;
+};
+hipError_t read_back(const aijhip_mat &M, HostCsr &H, bool values = true) {
+    H.ai.resize((size_t)M.m + 1);
+    H.aj.resize((size_t)M.nz);
+    H.aa.resize(values ? (size_t)M.nz : 0);
+    hipError_t e = hipMemcpy(H.ai.data(), M.d_ai, sizeof(int32_t) * H.ai.size(), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && M.nz > 0)
+        e = hipMemcpy(H.aj.data(), M.d_aj, sizeof(int32_t) * (size_t)M.nz, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && values && M.nz > 0)
+        e = hipMemcpy(H.aa.data(), M.d_aa, sizeof(double) * (size_t)M.nz, hipMemcpyDeviceToHost);
+    return e;
+}
+
+// A_(l+1)'s values by the host builder (a row past the numeric kernel's
+// classes: how the set-up sends such a level to the host), on operands read
+// back from the level handles, into the A_(l+1) handle's values
+int galerkin_refresh_host(aijhip_ksp *K, int32_t l) {
+    const aijhip_mat &Al = *K->mg[l].A, &Pl = *K->mg[l].P;
+    aijhip_mat &Ac = *K->mg[l + 1].A;
+    HostCsr a, p, c0;
+    hipError_t e;
+    if ((e = read_back(Al, a)) != hipSuccess || (e = read_back(Pl, p)) != hipSuccess ||
+        (e = read_back(Ac, c0, false)) != hipSuccess)
+        return cg_hip(e, "GAMG refresh: read level operands");
+    std::vector<int32_t> ci, cj;
+    std::vector<double> ca;
+    const int rc = aijhip_gamg::galerkin_host(Al.m, a.ai.data(), a.aj.data(), a.aa.data(), Pl.n, p.ai.data(),
+                                              p.aj.data(), p.aa.data(), K->gamg.threads, ci, cj, ca);
+    if (rc) return cg_fail(rc, "GAMG refresh: host Galerkin product failed");
+    if (ci != c0.ai || cj != c0.aj)
+        return cg_fail(AIJHIP_ERR_STATE, "GAMG refresh: the level operator's pattern is not the product's");
+    if (Ac.nz > 0 &&
+        (e = hipMemcpy(Ac.d_aa, ca.data(), sizeof(double) * (size_t)Ac.nz, hipMemcpyHostToDevice)) != hipSuccess)
+        return cg_hip(e, "GAMG refresh: level values");
+    return AIJHIP_OK;
+}
+
+// PCSetUp_GAMG with -pc_gamg_reuse_interpolation on new values of the same
+// structure (include/aijhip_ksp.h): every P_l, P_l^T and level pattern stays;
+// A_(l+1) = P_l^T (A_l P_l) goes into the existing level operators by the
+// numeric-only product (gamg_device.hip k_rowprod_numeric), then D^-1, the
+// fused-launch choices and the smoothers follow the new values.
+// AIJHIP_GAMG_LOG=1 prints the phases.
+int gamg_refresh(aijhip_ksp *K) {
+    aijhip::Range range("PCSetUp_GAMG (reuse interpolation)");
+    const bool log = std::getenv("AIJHIP_GAMG_LOG") != nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char *what, int32_t l) {
+        if (!log) return;
+        (void)hipDeviceSynchronize();
+        const auto t = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "gamg refresh level %d %-18s %8.3f ms\n", l, what,
+                     std::chrono::duration<double, std::milli>(t - t0).count());
+        t0 = t;
+    };
+    const int32_t nl = (int32_t)K->mg.size();
+    const int n_cu = std::max(K->A->n_cu, 1);
+    int rc = AIJHIP_OK;
+    hipError_t e = hipSuccess;
+    // AIJHIP_GAMG_REFRESH=host sends every level's products to the host
+    // builder (the path of a row past the numeric classes; the same bits)
+    const char *side = std::getenv("AIJHIP_GAMG_REFRESH");
+    const bool all_host = side && std::string(side) == "host";
+    for (int32_t l = 0; l + 1 < nl; ++l) {
+        MGLevel &L = K->mg[l];
+        aijhip_mat &Ac = *K->mg[l + 1].A;
+        if (all_host) K->host_level[l] = 1;
+        if (!L.P->transpose && (rc = aijhip_mat_mult_transpose(L.P, L.r, K->mg[l + 1].b, nullptr))) return rc;
+        const aijhip_gamg::DCsr Av = aijhip_gamg::csr_view(*L.A), Pv = aijhip_gamg::csr_view(*L.P),
+                                PTv = aijhip_gamg::csr_view(*L.P->transpose);
+        aijhip_gamg::DCsr &AP = K->ap[l];
+        bool host = K->host_level[l] != 0;
+        double *apv = nullptr;  // A P's values: transient
+        if (!host && !AP.ai) {
+            // no pattern yet (the flag was set after the set-up, or the host
+            // built the level): the symbolic product once, its values as they come
+            aijhip_gamg::DCsr T;
+            rc = aijhip_gamg::rowprod_device(Av, Pv, T, n_cu, nullptr);
+            if (rc == AIJHIP_ERR_STATE) host = true;
+            else if (rc) return rc;
+            else {
+                apv = T.aa;
+                T.aa = nullptr;
+                AP = T;
+            }
+            lap("A*P (symbolic)", l);
+        } else if (!host) {
+            if ((e = aijhip_gamg::dalloc(&apv, AP.nz + 2)) != hipSuccess) return cg_hip(e, "GAMG refresh: A P values");
+            rc = aijhip_gamg::rowprod_numeric_device(Av, Pv, AP.ai, AP.aj, apv, n_cu, &K->ap_cls[l]);
+            if (rc == AIJHIP_ERR_STATE) host = true;
+            else if (rc) {
+                hipFree(apv);
+                return rc;
+            }
+            lap("A*P (numeric)", l);
+        }
+        if (!host) {
+            aijhip_gamg::DCsr APv = AP;
+            APv.aa = apv;
+            rc = aijhip_gamg::rowprod_numeric_device(PTv, APv, Ac.d_ai, Ac.d_aj, Ac.d_aa, n_cu, &K->ac_cls[l]);
+            if (rc == AIJHIP_ERR_STATE) host = true;
+            else if (rc) {
+                hipFree(apv);
+                return rc;
+            }
+            lap("P^T*(AP) (numeric)", l);
+        }
+        if ((e = hipDeviceSynchronize()) != hipSuccess) {
+            hipFree(apv);
+            return cg_hip(e, "GAMG refresh: Galerkin product");
+        }
+        hipFree(apv);
+        if (host) {
+            K->host_level[l] = 1;
+            if ((rc = galerkin_refresh_host(K, l))) return rc;
+            lap("host Galerkin", l);
+        }
+        // the level handle's value copies and codes follow its new values
+        if ((rc = aijhip::values_changed(&Ac))) return rc;
+        lap("level handle", l);
+    }
+    for (int32_t l = 0; l < nl; ++l) {
+        MGLevel &L = K->mg[l];
+        if (L.m > 0)
+            hipLaunchKernelGGL(k_diag_inv, dim3((unsigned)((L.m + 255) / 256)), dim3(256), 0, nullptr, L.m,
+                               L.A->d_ai, L.A->d_aj, L.A->d_aa, L.dinv);
+        if (l == 0) {  // the finest plan may have gained or lost its templates
+            hipFree(L.tdinv);
+            L.tdinv = nullptr;
+            if (L.m > 0 && L.A->plan.d_pid && L.A->plan.d_pval && !std::getenv("AIJHIP_KSP_EXPLICIT_Z")) {
+                const int np = L.A->plan.n_pat;
+                if ((e = hipMalloc(&L.tdinv, sizeof(double) * (size_t)np)) != hipSuccess)
+                    return cg_hip(e, "GAMG: template D^-1");
+                hipLaunchKernelGGL(k_tmpl_dinv, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, nullptr, np,
+                                   L.A->plan.d_ptab, L.A->plan.d_pval, L.tdinv);
+            }
+        }
+        L.nnz = L.A->nz;
+        L.fused = !std::getenv("AIJHIP_MG_UNFUSED") && aijhip::stream_mg_fusable(*L.A);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return cg_hip(e, "GAMG refresh: D^-1");
+    lap("D^-1", -1);
+    for (int32_t l = 0; l + 1 < nl; ++l) {
+        MGLevel &L = K->mg[l];
+        double lambda = 0.0;
+        if (K->smoother.type == AIJHIP_MG_SMOOTH_CHEBYSHEV) {
+            // emax(D^-1 A_l) again, by the set-up's estimator: on the device
+            // where the level's plan serves it, else the host builder's
+            if (aijhip::stream_mg_fusable(*L.A)) {
+                if ((rc = aijhip_gamg::emax_device(*L.A, L.dinv, K->gamg.eig_its, K->gamg.eig_ksp == 1, &lambda)))
+                    return rc;
+            } else {
+                HostCsr a;
+                if ((e = read_back(*L.A, a)) != hipSuccess) return cg_hip(e, "GAMG refresh: read level operator");
+                lambda = aijhip_gamg::emax_host(L.m, a.ai.data(), a.aj.data(), a.aa.data(), K->gamg.eig_its,
+                                                K->gamg.eig_ksp, K->gamg.threads);
+            }
+        }
+        if ((rc = aijhip::mg_set_smoother(K->smoother, lambda, L))) return rc;
+        if (aijhip::mg_smoother_needs_w(L) && !L.w &&
+            (e = hipMalloc(&L.w, sizeof(double) * (size_t)std::max<int32_t>(L.m, 1))) != hipSuccess)
+            return cg_hip(e, "GAMG: smoother vector");
+    }
+    lap("smoothers", -1);
+    hipFree(K->d_mgpart);  // (the finest plan's blocks may have moved)
+    K->d_mgpart = nullptr;
+    if (K->mg[0].fused &&
+        (e = hipMalloc(&K->d_mgpart, sizeof(double) * 2 * (size_t)std::max(1, K->mg[0].A->plan.n_blocks))) !=
+            hipSuccess)
+        return cg_hip(e, "GAMG partials");
+    K->mgview.clear();
+    for (MGLevel &L : K->mg) {
+        L.Ad = L.A;
+        L.Pd = L.P;
+        K->mgview.push_back(L);
+    }
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return cg_hip(e, "GAMG refresh");
     return AIJHIP_OK;
 }
 
@@ -387,18 +598,62 @@ int aijhip_ksp_set_up(aijhip_ksp_t K) {
     const auto t0 = std::chrono::steady_clock::now();
     aijhip_mat *A = K->A;
     DeviceGuard g(A->device);
-    ksp_free(K);
-    int rc = cg_set_up(K->cg, *A, true);
-    if (!rc && K->cg.pc == AIJHIP_PC_GAMG) rc = gamg_setup(K);
+    // reuse-interpolation: a set-up GAMG handle whose operator kept its
+    // structure refreshes (CG's vectors and D^-1 follow the new plan and
+    // values; the hierarchy's interpolations, patterns and blocks stay)
+    const bool refresh = K->reuse_interp && K->set_up && K->cg.pc == AIJHIP_PC_GAMG && !K->mg.empty() &&
+                         K->s_gen == A->struct_gen;
+    int rc;
+    if (refresh) {
+        rc = cg_set_up(K->cg, *A, true);
+        if (!rc) rc = gamg_refresh(K);
+    } else {
+        ksp_free(K);
+        rc = cg_set_up(K->cg, *A, true);
+        if (!rc && K->cg.pc == AIJHIP_PC_GAMG) rc = gamg_setup(K);
+    }
     if (!rc) rc = reserve_mat_vcycle(K);
     if (rc) {
         ksp_free(K);
         return rc;
     }
     K->setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    ++(refresh ? K->n_refreshed : K->n_full);
     K->set_up = true;
     K->a_gen = A->plan_gen;
     K->v_gen = A->values_gen;
+    K->s_gen = A->struct_gen;
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_set_gamg_reuse_interpolation(aijhip_ksp_t K, int flg) {
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    K->reuse_interp = flg != 0;
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_get_gamg_reuse_interpolation(aijhip_ksp_t K, int *flg) {
+    if (!K || !flg) return cg_fail(AIJHIP_ERR_ARG, "NULL argument");
+    *flg = K->reuse_interp ? 1 : 0;
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_get_mat_vcycle_reserve(aijhip_ksp_t K, int32_t cap, uint64_t *ptrs, int32_t *n) {
+    if (!K || !n || (cap > 0 && !ptrs)) return cg_fail(AIJHIP_ERR_ARG, "NULL argument");
+    std::vector<uint64_t> all;
+    for (const aijhip::MGMultiBlocks::Level &L : K->mgm.lev)
+        for (const double *p : {L.b, L.x, L.r, L.w}) all.push_back((uint64_t)reinterpret_cast<uintptr_t>(p));
+    for (const double *p : {K->mm.d_r, K->mm.d_z, K->mm.d_p}) all.push_back((uint64_t)reinterpret_cast<uintptr_t>(p));
+    for (int32_t q = 0; q < std::min<int32_t>(cap, (int32_t)all.size()); ++q) ptrs[q] = all[(size_t)q];
+    *n = (int32_t)all.size();
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_get_gamg_setup_counts(aijhip_ksp_t K, int32_t *full, int32_t *refreshed, double *last_seconds) {
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    if (full) *full = K->n_full;
+    if (refreshed) *refreshed = K->n_refreshed;
+    if (last_seconds) *last_seconds = K->setup_seconds;
     return AIJHIP_OK;
 }
 

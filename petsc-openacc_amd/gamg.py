@@ -17,6 +17,7 @@ GAMG_SYMBOLS = (
     "aijhip_gamg_diag_rowprod", "aijhip_gamg_diag_rowprod_p0", "aijhip_gamg_diag_prolong",
     "aijhip_gamg_diag_tentative", "aijhip_gamg_diag_info", "aijhip_gamg_diag_get_csr",
     "aijhip_gamg_diag_get_passes", "aijhip_gamg_diag_destroy",
+    "aijhip_gamg_diag_rowprod_numeric", "aijhip_gamg_diag_numeric_classes",
 )
 SMOOTHER_TYPES = {"richardson": 0, "chebyshev": 1}
 
@@ -68,6 +69,9 @@ def _lib():
         L.aijhip_gamg_diag_get_csr.argtypes = [_P, _P, _P, _P]
         L.aijhip_gamg_diag_get_passes.argtypes = [_P, _P, _P]
         L.aijhip_gamg_diag_destroy.argtypes = [_P]
+        L.aijhip_gamg_diag_rowprod_numeric.argtypes = [i32, i32, i32, _P, _P, _P, _P, _P, _P, _P, _P, i32,
+                                                       ctypes.POINTER(_P)]
+        L.aijhip_gamg_diag_numeric_classes.argtypes = [_P, i32, ctypes.POINTER(i32)]
         _bound = True
     return L
 
@@ -183,6 +187,34 @@ def device_rowprod(A, B, n, n_cu=0):
     rc = L.aijhip_gamg_diag_rowprod(len(ai) - 1, len(bi) - 1, int(n), ai.ctypes.data, aj.ctypes.data, aa.ctypes.data,
                                     bi.ctypes.data, bj.ctypes.data, ba.ctypes.data, int(n_cu), ctypes.byref(h))
     return _diag_result(L, rc, h)
+
+
+def device_rowprod_numeric(A, B, n, ci, cj, n_cu=0):
+    """The values of C = A B on the known pattern (ci, cj ascending per row)
+    through the refresh's numeric-only kernel. Returns ((ci, cj, ca), report);
+    report["passes"] = [(lanes, capacity, "write", capacity)] per launch."""
+    L = _lib()
+    ai, aj, aa = _csr_args(*A)
+    bi, bj, ba = _csr_args(*B)
+    ci = np.ascontiguousarray(ci, dtype=np.int32)
+    cj = np.ascontiguousarray(cj, dtype=np.int32)
+    if len(ci) != len(ai) or len(cj) != ci[-1]:
+        raise ValueError("the pattern does not fit A's rows")
+    h = _P()
+    rc = L.aijhip_gamg_diag_rowprod_numeric(len(ai) - 1, len(bi) - 1, int(n), ai.ctypes.data, aj.ctypes.data,
+                                            aa.ctypes.data, bi.ctypes.data, bj.ctypes.data, ba.ctypes.data,
+                                            ci.ctypes.data, cj.ctypes.data, int(n_cu), ctypes.byref(h))
+    return _diag_result(L, rc, h)
+
+
+def numeric_classes():
+    """[(lanes, capacity)]: every instantiation of the numeric-only kernel."""
+    L = _lib()
+    n = ctypes.c_int32()
+    _pkg._check(L.aijhip_gamg_diag_numeric_classes(None, 0, ctypes.byref(n)))
+    pairs = np.zeros((max(n.value, 1), 2), np.int32)
+    _pkg._check(L.aijhip_gamg_diag_numeric_classes(pairs.ctypes.data, n.value, ctypes.byref(n)))
+    return [(int(g), int(c)) for g, c in pairs[: n.value]]
 
 
 def device_rowprod_p0(A, agg, p0, na, n_cu=0):

@@ -33,7 +33,8 @@ KSP_SYMBOLS = (
     "aijhip_ksp_mat_solve", "aijhip_ksp_mat_solve_host", "aijhip_ksp_get_mat_solve_results",
     "aijhip_ksp_get_mat_solve_history", "aijhip_ksp_get_mat_solve_bytes",
     "aijhip_ksp_set_mat_vcycle_width", "aijhip_ksp_get_mat_vcycle_width", "aijhip_ksp_pc_apply",
-    "aijhip_ksp_pc_mat_apply",
+    "aijhip_ksp_pc_mat_apply", "aijhip_ksp_set_gamg_reuse_interpolation", "aijhip_ksp_get_gamg_reuse_interpolation",
+    "aijhip_ksp_get_gamg_setup_counts", "aijhip_ksp_get_mat_vcycle_reserve",
 )
 KSP_MAX_RHS = 64  # AIJHIP_KSP_MAX_RHS
 _P = ctypes.c_void_p
@@ -84,6 +85,11 @@ def _lib():
         L.aijhip_ksp_get_mat_vcycle_width.argtypes = [_P, ctypes.POINTER(ctypes.c_int32)]
         L.aijhip_ksp_pc_apply.argtypes = [_P, _P, _P, _P]
         L.aijhip_ksp_pc_mat_apply.argtypes = L.aijhip_ksp_mat_solve.argtypes
+        L.aijhip_ksp_set_gamg_reuse_interpolation.argtypes = [_P, ctypes.c_int]
+        L.aijhip_ksp_get_gamg_reuse_interpolation.argtypes = [_P, ctypes.POINTER(ctypes.c_int)]
+        L.aijhip_ksp_get_gamg_setup_counts.argtypes = [_P, ctypes.POINTER(ctypes.c_int32),
+                                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]
+        L.aijhip_ksp_get_mat_vcycle_reserve.argtypes = [_P, ctypes.c_int32, _P, ctypes.POINTER(ctypes.c_int32)]
         _bound = True
     return L
 
@@ -92,12 +98,15 @@ class KSPCG:
     """KSPCG on a SeqAIJHIP operator (device vectors)."""
 
     def __init__(self, A, rtol=1e-5, atol=1e-50, dtol=1e5, max_it=10000, pc="jacobi",
-                 norm="preconditioned", guess_nonzero=False, gamg=None, smoother=None, mat_vcycle=0):
+                 norm="preconditioned", guess_nonzero=False, gamg=None, smoother=None, mat_vcycle=0,
+                 reuse_interpolation=False):
         """gamg: aijhip_gamg_params_t fields; smoother: the GAMG level smoother,
         dict(type="richardson"|"chebyshev", its=, scale=, lo=, hi=) (gamg.mg_smoother;
         None: Richardson(1), scale 1); mat_vcycle: the widest block mat_solve and
         pc_mat_apply take with pc="gamg" (aijhip_ksp_set_mat_vcycle_width; 0: they
-        refuse a GAMG handle)."""
+        refuse a GAMG handle); reuse_interpolation: -pc_gamg_reuse_interpolation, new
+        values on the same structure refresh the hierarchy instead of rebuilding it
+        (aijhip_ksp_set_gamg_reuse_interpolation)."""
         L = _lib()
         self.A = A
         self._h = _P()
@@ -116,6 +125,37 @@ class KSPCG:
         _pkg._check(L.aijhip_ksp_set_initial_guess_nonzero(self._h, int(guess_nonzero)))
         if mat_vcycle:
             self.set_mat_vcycle_width(mat_vcycle)
+        if reuse_interpolation:
+            self.reuse_interpolation = True
+
+    @property
+    def reuse_interpolation(self) -> bool:
+        v = ctypes.c_int()
+        _pkg._check(_lib().aijhip_ksp_get_gamg_reuse_interpolation(self._h, ctypes.byref(v)))
+        return bool(v.value)
+
+    @reuse_interpolation.setter
+    def reuse_interpolation(self, flg):
+        _pkg._check(_lib().aijhip_ksp_set_gamg_reuse_interpolation(self._h, int(bool(flg))))
+
+    def setup_counts(self):
+        """(full set-ups, refreshes, seconds of the last of either) of this
+        handle (aijhip_ksp_get_gamg_setup_counts)."""
+        full, ref, secs = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+        _pkg._check(_lib().aijhip_ksp_get_gamg_setup_counts(self._h, ctypes.byref(full), ctypes.byref(ref),
+                                                            ctypes.byref(secs)))
+        return full.value, ref.value, secs.value
+
+    def mat_vcycle_reserve(self):
+        """Device addresses of the reserved multi-column blocks (b, x, r, w per
+        level) followed by the lock-step work vectors R, Z, P
+        (aijhip_ksp_get_mat_vcycle_reserve): equal tuples mean kept allocations."""
+        n = ctypes.c_int32()
+        L = _lib()
+        _pkg._check(L.aijhip_ksp_get_mat_vcycle_reserve(self._h, 0, None, ctypes.byref(n)))
+        ptrs = np.zeros(max(n.value, 1), np.uint64)
+        _pkg._check(L.aijhip_ksp_get_mat_vcycle_reserve(self._h, n.value, ptrs.ctypes.data, ctypes.byref(n)))
+        return tuple(int(p) for p in ptrs[: n.value])
 
     def set_mat_vcycle_width(self, kmax: int):
         """Reserve the multi-column V-cycle's level blocks for kmax columns (at

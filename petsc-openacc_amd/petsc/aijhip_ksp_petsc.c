@@ -176,7 +176,7 @@ static PetscErrorCode KSPSetUp_CGHIP(KSP ksp)
   aijhip_gamg_params_t gp;
   PetscInt             iv;
   PetscReal            rv;
-  PetscBool            set;
+  PetscBool            set, reuse = PETSC_FALSE;
   int                  pc, nt, rc;
   PetscErrorCode       ierr;
 
@@ -192,9 +192,22 @@ static PetscErrorCode KSPSetUp_CGHIP(KSP ksp)
   ierr = KSPCGHIPStandIn(ksp);CHKERRQ(ierr);
   ierr = PetscObjectStateGet((PetscObject)A, &state);CHKERRQ(ierr);
   if (c->k && c->h == h && c->state == state && c->pc == pc) PetscFunctionReturn(0);
+  /* -pc_gamg_reuse_interpolation: the same handle with a new state (MatAssemblyEnd's
+     aijhip_mat_update_values, or aijhip_mat_assembly_end) keeps its KSP; the library
+     refreshes the hierarchy on the same structure and rebuilds it on a new one */
+  ierr = PetscOptionsGetBool(NULL, NULL, "-pc_gamg_reuse_interpolation", &reuse, NULL);CHKERRQ(ierr);
+  if (reuse && c->k && c->h == h && c->pc == pc && pc == AIJHIP_PC_GAMG) {
+    rc = aijhip_ksp_set_tolerances(c->k, ksp->rtol, ksp->abstol, ksp->divtol, (int32_t)ksp->max_it);
+    if (!rc) rc = aijhip_ksp_set_up(c->k);
+    if (rc) SETERRQ1(PetscObjectComm((PetscObject)ksp), PETSC_ERR_LIB, "aijhip: %s", aijhip_last_error());
+    c->state = state;
+    PetscFunctionReturn(0);
+  }
   ierr = KSPCGHIPFree(c);CHKERRQ(ierr);
   rc = aijhip_ksp_create(h, &c->k);
   if (!rc) rc = aijhip_ksp_set_pc_type(c->k, pc);
+  /* (before the first set-up, so that it keeps the patterns the refreshes reuse) */
+  if (!rc && reuse && pc == AIJHIP_PC_GAMG) rc = aijhip_ksp_set_gamg_reuse_interpolation(c->k, 1);
   if (!rc && pc == AIJHIP_PC_GAMG) {
     aijhip_gamg_params_default(&gp);
     ierr = PetscOptionsGetReal(NULL, NULL, "-pc_gamg_threshold", &rv, &set);CHKERRQ(ierr);
