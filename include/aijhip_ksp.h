@@ -60,12 +60,14 @@ enum {
     AIJHIP_KSP_CONVERGED_ATOL = 3,
     AIJHIP_KSP_DIVERGED_ITS = -3,
     AIJHIP_KSP_DIVERGED_DTOL = -4,
+    AIJHIP_KSP_DIVERGED_BREAKDOWN = -5, /* BiCGStab: v.rp = 0, t = 0 with s != 0, or rho = 0 */
     AIJHIP_KSP_DIVERGED_INDEFINITE_PC = -8,
     AIJHIP_KSP_DIVERGED_NANORINF = -9,
     AIJHIP_KSP_DIVERGED_INDEFINITE_MAT = -10
 };
 
-/* KSPCreate + KSPSetOperators(A, A) + KSPSetType(KSPCG). A must be square;
+/* KSPCreate + KSPSetOperators(A, A) + KSPSetType(KSPCG) (aijhip_ksp_set_type
+ * chooses another type). A must be square;
  * the handle borrows A (A must outlive it). Defaults as PETSc: rtol 1e-5,
  * atol 1e-50, dtol 1e5, max_it 10000, PC Jacobi, preconditioned norm,
  * zero initial guess. */
@@ -73,6 +75,51 @@ int aijhip_ksp_create(aijhip_mat_t A, aijhip_ksp_t *ksp);
 int aijhip_ksp_set_tolerances(aijhip_ksp_t ksp, double rtol, double abstol, double dtol,
                               int32_t max_it);
 int aijhip_ksp_set_pc_type(aijhip_ksp_t ksp, int pc_type);
+
+/* KSPType: KSPCG (the default) and KSPBCGS. */
+enum { AIJHIP_KSP_CG = 0, AIJHIP_KSP_BCGS = 1 };
+
+/* KSPSetType / KSPGetType. An unknown type is AIJHIP_ERR_ARG. A change of type
+ * keeps the PC: a GAMG hierarchy that is set up stays set up
+ * (aijhip_ksp_get_gamg_setup_counts does not move); BiCGStab's extra work
+ * vectors are allocated by the next aijhip_ksp_set_up or solve and freed with
+ * the handle, so a solve on a handle that is set up allocates nothing.
+ *
+ * AIJHIP_KSP_BCGS: preconditioned BiCGStab for nonsymmetric operators, on the
+ * device from the first residual to the last update. It restates PETSc 3.7.6
+ * KSPSolve_BCGS [ext] (src/ksp/ksp/impls/bcgs/bcgs.c) with left
+ * preconditioning, K(y) = B^-1 (A y) with B the handle's PC, and
+ * KSPConvergedDefault [ext]:
+ *
+ *   x = 0 (or the caller's x);  r = B^-1 (b - A x);  dp = |r|;  hist[0] = dp
+ *   converged(0, dp, snorm)     snorm = dp, or |B^-1 b| with a nonzero guess
+ *   max_it <= 0: DIVERGED_ITS at iteration 0
+ *   rp = r;  rhoold = alpha = omegaold = 1;  p = v = 0
+ *   loop:  rho = r.rp;  beta = (rho / rhoold) (alpha / omegaold)
+ *          p = r - (omegaold beta) v + beta p
+ *          v = K(p);  d1 = v.rp;  d1 = 0: DIVERGED_BREAKDOWN (x untouched)
+ *          alpha = rho / d1;  s = r - alpha v
+ *          t = K(s);  d1 = s.t;  d2 = t.t
+ *          d2 = 0: s.s != 0 is DIVERGED_BREAKDOWN; else x += alpha p,
+ *                  its += 1, the norm is 0 and the reason CONVERGED_RTOL
+ *          omega = d1 / d2;  x += alpha p + omega s;  r = s - omega t
+ *          dp = |r|;  its += 1;  hist[its] = dp;  converged(its, dp)
+ *          rho = 0: DIVERGED_BREAKDOWN;  its = max_it: DIVERGED_ITS
+ *
+ * One deliberate difference from PETSc: with max_it = 0 PETSc's do-while runs
+ * one iteration; this solver stops at iteration 0 with DIVERGED_ITS, as this
+ * library's CG does.
+ *
+ * Under AIJHIP_KSP_BCGS aijhip_ksp_solve, _solve_host and the getters of the
+ * last solve (iteration number, residual norm, reason, history, host syncs)
+ * serve BiCGStab; the tolerances, the initial-guess flag and AIJHIP_KSP_POLL
+ * apply; aijhip_ksp_get_fused reports 0. Only the preconditioned norm is
+ * served (the other norm types need right preconditioning): aijhip_ksp_solve
+ * with another norm type returns AIJHIP_ERR_STATE before any device work, and
+ * so do aijhip_ksp_mat_solve and _mat_solve_host, whose lock-step solver is
+ * CG. aijhip_ksp_pc_apply and _pc_mat_apply do not depend on the type. */
+int aijhip_ksp_set_type(aijhip_ksp_t ksp, int type);
+int aijhip_ksp_get_type(aijhip_ksp_t ksp, int *type);
 int aijhip_ksp_set_norm_type(aijhip_ksp_t ksp, int norm_type);
 int aijhip_ksp_set_initial_guess_nonzero(aijhip_ksp_t ksp, int flg);
 /* KSPSetUp: PC set-up (inverse diagonal) and work vectors. Called by solve
@@ -121,7 +168,21 @@ int aijhip_ksp_get_host_syncs(aijhip_ksp_t ksp, int32_t *n);
  * 48 m (the other Chebyshev steps).
  * The per-part split: *spmv_bytes of the total are matrix launches, *level0
  * of the total belong to the finest level (its SpMVs and vectors). Valid
- * after set-up; the first iteration moves a little less. */
+ * after set-up; the first iteration moves a little less.
+ *
+ * A BiCGStab handle (AIJHIP_KSP_BCGS) reports one BiCGStab iteration, with m
+ * rows: two products at mult_layout_bytes each, two PC applications (GAMG:
+ * two V-cycles, each counted as above) and the five vector passes
+ *   p = r - (omegaold beta) v + beta p        32 m  (reads r, p, v; writes p)
+ *   v = D^-1 v with the v.rp partials         32 m  (reads v, D^-1, rp; writes v;
+ *                                                    none / GAMG 16 m: reads v, rp)
+ *   s = r - alpha v                           24 m  (reads r, v; writes s)
+ *   t = D^-1 t with s.t, t.t, s.s             32 m  (reads t, D^-1, s; writes t;
+ *                                                    none / GAMG 16 m: reads t, s)
+ *   x += alpha p + omega s, r = s - omega t   56 m  (reads x, p, s, t, rp;
+ *   with r.r, r.rp                                   writes x, r)
+ *   *bytes = 2 mult_layout_bytes + 176 m (Jacobi), + 144 m (none, and GAMG
+ *   beside its two V-cycles). */
 int aijhip_ksp_get_iteration_bytes(aijhip_ksp_t ksp, int64_t *bytes, int64_t *spmv_bytes, int64_t *level0);
 /* GAMG options (before set-up); NULL = PETSc defaults
  * (aijhip_gamg_params_default). */

@@ -311,7 +311,7 @@ class KSPCGMPINative:
         per rank's diagonal block); gamg = the GAMG parameters; smoother = the
         GAMG level smoother (ksp.KSPCG's keyword); graph: the
         poll batch replayed as a captured HIP graph (None: the library's
-        default, on over RCCL; False / True)."""
+        default, off; False / True, on only over RCCL)."""
         K = importlib.import_module("petsc-openacc_amd.ksp")
         L = _lib()
         self.op = op

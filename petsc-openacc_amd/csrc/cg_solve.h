@@ -72,6 +72,12 @@ struct CGOperator {
     // honours the stop flag S->done and, when the set-up is fused, leaves the
     // n_dparts p.w partials in part (and the A_o list in opart).
     virtual int apply(const double *x, double *y, hipStream_t s, double *part, const CGState *S) = 0;
+    // the plain product under a device stop flag (BiCGStab's, bcgs_solve.hip):
+    // y may be left unwritten once *stop is set. An operator whose product
+    // takes no flag runs the plain product: nothing reads y after the stop.
+    virtual int apply_stop(const double *x, double *y, hipStream_t s, const int * /*stop*/) {
+        return apply(x, y, s, nullptr, nullptr);
+    }
     // in-place sum of red[0, n) over the ranks (multi only)
     virtual int allreduce(double *, int, hipStream_t) { return AIJHIP_OK; }
     // z = B r, one V-cycle (vcycle only). dots != NULL: *dots = the z.z / z.r

@@ -23,6 +23,7 @@
 #include "gamg_device.h"
 #include "aijhip_internal.h"
 #include "aijhip_ksp.h"
+#include "bcgs_solve.h"
 #include "cg_multi.h"
 #include "cg_solve.h"
 #include "mg_cycle.h"
@@ -53,6 +54,8 @@ struct aijhip_ksp {
     // (Those A/B forms were withdrawn in round 4.)
     CGSolve cg;
     CGMulti mm;  // KSPMatSolve's work vectors and per-column results (cg_multi.hip)
+    int type = AIJHIP_KSP_CG;  // KSPType (aijhip_ksp_set_type); a change keeps the PC
+    BCGSWork bw;               // BiCGStab's vectors beyond CG's (bcgs_solve.hip)
     aijhip_gamg_params_t gamg;
     aijhip_mg_smoother_t smoother;  // of every GAMG level but the coarsest (aijhip_ksp_set_mg_smoother)
     bool set_up = false;
@@ -109,6 +112,7 @@ void ksp_free(aijhip_ksp *K) {
     mg_free(K);
     cg_free(K->cg);
     cgm_free(K->mm);
+    bcgs_free(K->bw);
     hipFree(K->d_hb); hipFree(K->d_hx);
     K->d_hb = K->d_hx = nullptr;
     K->set_up = false;
@@ -159,6 +163,10 @@ struct KspOperator final : CGOperator {
         const hipError_t e = part && K->cg.fused ? aijhip::launch_stream_dot(*K->A, x, y, part, &S->done, s)
                                                  : aijhip::launch_mult(*K->A, x, nullptr, y, false, s,
                                                                        part ? &S->done : nullptr);
+        return e == hipSuccess ? AIJHIP_OK : cg_hip(e, "KSPSolve product");
+    }
+    int apply_stop(const double *x, double *y, hipStream_t s, const int *stop) override {
+        const hipError_t e = aijhip::launch_mult(*K->A, x, nullptr, y, false, s, stop);
         return e == hipSuccess ? AIJHIP_OK : cg_hip(e, "KSPSolve product");
     }
     int pc_apply(const double *r, double *z, hipStream_t s, const int *stop, const double **dots,
@@ -516,7 +524,7 @@ int aijhip_ksp_create(aijhip_mat_t A, aijhip_ksp_t *out) {
     if (!out) return cg_fail(AIJHIP_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (!A) return cg_fail(AIJHIP_ERR_ARG, "NULL matrix");
-    if (A->m != A->n) return cg_fail(AIJHIP_ERR_ARG, "CG needs a square operator");
+    if (A->m != A->n) return cg_fail(AIJHIP_ERR_ARG, "KSP needs a square operator");
     aijhip_ksp *K = new (std::nothrow) aijhip_ksp();
     if (!K) return cg_fail(AIJHIP_ERR_ALLOC, "host allocation");
     K->A = A;
@@ -542,6 +550,20 @@ int aijhip_ksp_set_pc_type(aijhip_ksp_t K, int pc) {
     K->cg.pc = pc;
     if (pc == AIJHIP_PC_GAMG)  // the set-up's streams, made once per process
         for (int slot = 0; slot < 2; ++slot) (void)aijhip_gamg::setup_stream(K->A->device, slot);
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_set_type(aijhip_ksp_t K, int type) {
+    if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    if (type != AIJHIP_KSP_CG && type != AIJHIP_KSP_BCGS)
+        return cg_fail(AIJHIP_ERR_ARG, "unknown KSP type " + std::to_string(type) + " (AIJHIP_KSP_CG, AIJHIP_KSP_BCGS)");
+    K->type = type;  // the PC and its set-up stay; BiCGStab's vectors come with the next set_up or solve
+    return AIJHIP_OK;
+}
+
+int aijhip_ksp_get_type(aijhip_ksp_t K, int *type) {
+    if (!K || !type) return cg_fail(AIJHIP_ERR_ARG, "NULL argument");
+    *type = K->type;
     return AIJHIP_OK;
 }
 
@@ -594,7 +616,11 @@ int aijhip_ksp_set_initial_guess_nonzero(aijhip_ksp_t K, int flg) {
 int aijhip_ksp_set_up(aijhip_ksp_t K) {
     aijhip::Range range("KSPSetUp");
     if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
-    if (K->set_up && K->a_gen == K->A->plan_gen && K->v_gen == K->A->values_gen) return AIJHIP_OK;
+    if (K->set_up && K->a_gen == K->A->plan_gen && K->v_gen == K->A->values_gen) {
+        if (K->type != AIJHIP_KSP_BCGS) return AIJHIP_OK;
+        DeviceGuard g(K->A->device);  // a type set after the set-up: its vectors now, the PC as it is
+        return bcgs_reserve(K->bw, K->A->m);
+    }
     const auto t0 = std::chrono::steady_clock::now();
     aijhip_mat *A = K->A;
     DeviceGuard g(A->device);
@@ -613,6 +639,7 @@ int aijhip_ksp_set_up(aijhip_ksp_t K) {
         if (!rc && K->cg.pc == AIJHIP_PC_GAMG) rc = gamg_setup(K);
     }
     if (!rc) rc = reserve_mat_vcycle(K);
+    if (!rc && K->type == AIJHIP_KSP_BCGS) rc = bcgs_reserve(K->bw, A->m);
     if (rc) {
         ksp_free(K);
         return rc;
@@ -660,6 +687,10 @@ int aijhip_ksp_get_gamg_setup_counts(aijhip_ksp_t K, int32_t *full, int32_t *ref
 int aijhip_ksp_solve(aijhip_ksp_t K, const double *b, double *x, void *stream) {
     aijhip::Range range("KSPSolve");
     if (!K) return cg_fail(AIJHIP_ERR_ARG, "NULL ksp");
+    if (K->type == AIJHIP_KSP_BCGS && K->cg.normtype != AIJHIP_KSP_NORM_PRECONDITIONED)
+        return cg_fail(AIJHIP_ERR_STATE,
+                       "BiCGStab serves the preconditioned norm only: it preconditions from the left, and the "
+                       "other norm types need right preconditioning (aijhip_ksp_set_norm_type)");
     const int rc = aijhip_ksp_set_up(K);
     if (rc) return rc;
     DeviceGuard g(K->A->device);
@@ -667,6 +698,8 @@ int aijhip_ksp_solve(aijhip_ksp_t K, const double *b, double *x, void *stream) {
     K->cg.poll = 8;
     if (const char *v = std::getenv("AIJHIP_KSP_POLL")) K->cg.poll = std::max(1, std::atoi(v));
     KspOperator op(K);
+    if (K->type == AIJHIP_KSP_BCGS)
+        return bcgs_solve(K->cg, K->bw, op, b, x, reinterpret_cast<hipStream_t>(stream));
     return cg_solve(K->cg, op, b, x, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -714,7 +747,18 @@ int aijhip_ksp_get_iteration_bytes(aijhip_ksp_t K, int64_t *bytes, int64_t *spmv
     // template id instead of z; the update reads r, w and an id, writes r)
     int64_t spmv = a0, vec = K->cg.implicit_z ? 41 * m + 25 * m : 40 * m + (K->cg.pc == AIJHIP_PC_GAMG ? 24 * m : 40 * m);
     if (!K->cg.fused) vec += 16 * m;  // p . w in its own pass
-    int64_t lev0 = a0 + vec;
+    // BiCGStab: two products, two PC applications (nk) and its five vector
+    // passes: p = r - (omegaold beta) v + beta p 32 m; v = D^-1 v with v.rp
+    // 32 m (none / GAMG: 16 m, v and rp read only); s = r - alpha v 24 m;
+    // t = D^-1 t with s.t, t.t, s.s 32 m (none / GAMG: 16 m); the x / r
+    // update with r.r, r.rp 56 m (reads x, p, s, t, rp; writes x, r)
+    const bool bcgs = K->type == AIJHIP_KSP_BCGS;
+    const int64_t nk = bcgs ? 2 : 1;
+    if (bcgs) {
+        spmv = 2 * a0;
+        vec = (K->cg.pc == AIJHIP_PC_JACOBI ? 176 : 144) * m;
+    }
+    int64_t lev0 = spmv + vec;
     if (K->cg.pc == AIJHIP_PC_GAMG) {
         const int nl = (int)K->mg.size();
         for (int l = 0; l < nl; ++l) {
@@ -745,9 +789,9 @@ int aijhip_ksp_get_iteration_bytes(aijhip_ksp_t K, int64_t *bytes, int64_t *spmv
                     v += 2 * (k - 1) * (L.fused ? 8 + D : 40) * ml;
                 }
             }
-            spmv += sp;
-            vec += v;
-            if (l == 0) lev0 += sp + v;
+            spmv += nk * sp;
+            vec += nk * v;
+            if (l == 0) lev0 += nk * (sp + v);
         }
     }
     *bytes = spmv + vec;
@@ -758,7 +802,7 @@ int aijhip_ksp_get_iteration_bytes(aijhip_ksp_t K, int64_t *bytes, int64_t *spmv
 
 int aijhip_ksp_get_fused(aijhip_ksp_t K, int *fused) {
     if (!K || !fused) return cg_fail(AIJHIP_ERR_ARG, "NULL argument");
-    *fused = K->cg.fused ? 1 : 0;
+    *fused = K->type == AIJHIP_KSP_CG && K->cg.fused ? 1 : 0;
     return AIJHIP_OK;
 }
 
@@ -871,6 +915,10 @@ const char *const kNoWidth =
     "KSPMatSolve serves PC none and Jacobi: the V-cycle has no multi-column "
     "form (solve the columns one by one with aijhip_ksp_solve)";
 
+const char *const kNoBcgsMat =
+    "KSPMatSolve's lock-step solver is CG: a BiCGStab handle (AIJHIP_KSP_BCGS) solves the columns one by one "
+    "with aijhip_ksp_solve";
+
 // Whether the handle's PC has a multi-column form at width k: none and Jacobi
 // always, GAMG within the reserved width (aijhip_ksp_set_mat_vcycle_width)
 int mat_width_check(aijhip_ksp_t K, int32_t k) {
@@ -912,6 +960,7 @@ extern "C" {
 int aijhip_ksp_mat_solve(aijhip_ksp_t K, int32_t k, int layout, const double *B, int64_t ldb, double *X, int64_t ldx,
                          void *stream) {
     aijhip::Range range("KSPMatSolve");
+    if (K && K->type == AIJHIP_KSP_BCGS) return cg_fail(AIJHIP_ERR_STATE, kNoBcgsMat);
     int go = 0;
     int rc = mat_solve_check(K, k, layout, B, ldb, X, ldx, &go);
     if (rc || !go) return rc;
@@ -994,6 +1043,7 @@ int aijhip_ksp_pc_mat_apply(aijhip_ksp_t K, int32_t k, int layout, const double 
 
 int aijhip_ksp_mat_solve_host(aijhip_ksp_t K, int32_t k, int layout, const double *B, int64_t ldb, double *X,
                               int64_t ldx) {
+    if (K && K->type == AIJHIP_KSP_BCGS) return cg_fail(AIJHIP_ERR_STATE, kNoBcgsMat);
     int go = 0;
     int rc = mat_solve_check(K, k, layout, B, ldb, X, ldx, &go);
     if (rc || !go) return rc;

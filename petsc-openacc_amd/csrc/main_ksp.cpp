@@ -3,7 +3,7 @@
 // it with device-resident CG, print the same result block
 // (main_ksp.cpp:124-129), so scripts/generate_plots.py's regex still parses it.
 //
-//   main_ksp [-config FILE] [-da_grid_x N] [-da_grid_y N] [-da_grid_z N]
+//   main_ksp [-config FILE] [-da_grid_x N] [-da_grid_y N] [-da_grid_z N] [-ksp_type cg|bcgs]
 //            [-ksp_rtol R] [-ksp_atol A] [-ksp_max_it K] [-pc_type jacobi|none|gamg]
 //            [-ksp_norm_type preconditioned|unpreconditioned|natural]
 //            [-pc_gamg_threshold T] [-pc_gamg_agg_nsmooths S]
@@ -97,8 +97,8 @@ int main(int argc, char **argv) {
     const int32_t nx = (int32_t)geti("-da_grid_x", 100), ny = (int32_t)geti("-da_grid_y", 100),
                   nz = (int32_t)geti("-da_grid_z", 100);
     const std::string ksp_type = gets("-ksp_type", "cg");
-    if (ksp_type != "cg") {
-        std::fprintf(stderr, "main_ksp: -ksp_type %s not supported (cg only)\n", ksp_type.c_str());
+    if (ksp_type != "cg" && ksp_type != "bcgs") {
+        std::fprintf(stderr, "main_ksp: -ksp_type %s not supported (cg or bcgs)\n", ksp_type.c_str());
         return 1;
     }
     std::string pc_type = gets("-pc_type", "jacobi");
@@ -206,6 +206,7 @@ int main(int argc, char **argv) {
     // -------- KSPCreate / SetOperators / SetType(CG) / SetFromOptions / SetUp (:92-97)
     aijhip_ksp_t ksp = nullptr;
     CHK(aijhip_ksp_create(A, &ksp));
+    if (ksp_type == "bcgs") CHK(aijhip_ksp_set_type(ksp, AIJHIP_KSP_BCGS));
     CHK(aijhip_ksp_set_tolerances(ksp, getd("-ksp_rtol", 1e-5), getd("-ksp_atol", 1e-50),
                                   getd("-ksp_divtol", 1e5), (int32_t)geti("-ksp_max_it", 10000)));
     CHK(aijhip_ksp_set_pc_type(ksp, pc));

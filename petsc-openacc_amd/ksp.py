@@ -20,8 +20,10 @@ _pkg = importlib.import_module("petsc-openacc_amd")
 
 PC_TYPES = {"none": 0, "jacobi": 1, "gamg": 2, "bjacobi_gamg": 3}
 NORM_TYPES = {"none": 0, "preconditioned": 1, "unpreconditioned": 2, "natural": 3}
+KSP_TYPES = {"cg": 0, "bcgs": 1}
+DIVERGED_BREAKDOWN = -5  # AIJHIP_KSP_DIVERGED_BREAKDOWN (BiCGStab)
 REASONS = {2: "CONVERGED_RTOL", 3: "CONVERGED_ATOL", -3: "DIVERGED_ITS", -4: "DIVERGED_DTOL",
-           -8: "DIVERGED_INDEFINITE_PC", -9: "DIVERGED_NANORINF", -10: "DIVERGED_INDEFINITE_MAT"}
+           -5: "DIVERGED_BREAKDOWN", -8:"DIVERGED_INDEFINITE_PC", -9: "DIVERGED_NANORINF", -10: "DIVERGED_INDEFINITE_MAT"}
 KSP_SYMBOLS = (
     "aijhip_ksp_create", "aijhip_ksp_set_tolerances", "aijhip_ksp_set_pc_type", "aijhip_ksp_set_norm_type",
     "aijhip_ksp_set_initial_guess_nonzero", "aijhip_ksp_set_up", "aijhip_ksp_solve",
@@ -35,6 +37,7 @@ KSP_SYMBOLS = (
     "aijhip_ksp_set_mat_vcycle_width", "aijhip_ksp_get_mat_vcycle_width", "aijhip_ksp_pc_apply",
     "aijhip_ksp_pc_mat_apply", "aijhip_ksp_set_gamg_reuse_interpolation", "aijhip_ksp_get_gamg_reuse_interpolation",
     "aijhip_ksp_get_gamg_setup_counts", "aijhip_ksp_get_mat_vcycle_reserve",
+    "aijhip_ksp_set_type", "aijhip_ksp_get_type",
 )
 KSP_MAX_RHS = 64  # AIJHIP_KSP_MAX_RHS
 _P = ctypes.c_void_p
@@ -90,6 +93,8 @@ def _lib():
         L.aijhip_ksp_get_gamg_setup_counts.argtypes = [_P, ctypes.POINTER(ctypes.c_int32),
                                                        ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]
         L.aijhip_ksp_get_mat_vcycle_reserve.argtypes = [_P, ctypes.c_int32, _P, ctypes.POINTER(ctypes.c_int32)]
+        L.aijhip_ksp_set_type.argtypes = [_P, ctypes.c_int]
+        L.aijhip_ksp_get_type.argtypes = [_P, ctypes.POINTER(ctypes.c_int)]
         _bound = True
     return L
 
@@ -99,8 +104,9 @@ class KSPCG:
 
     def __init__(self, A, rtol=1e-5, atol=1e-50, dtol=1e5, max_it=10000, pc="jacobi",
                  norm="preconditioned", guess_nonzero=False, gamg=None, smoother=None, mat_vcycle=0,
-                 reuse_interpolation=False):
-        """gamg: aijhip_gamg_params_t fields; smoother: the GAMG level smoother,
+                 reuse_interpolation=False, ksp_type="cg"):
+        """ksp_type: "cg" or "bcgs" (aijhip_ksp_set_type; KSPBCGS is the latter);
+        gamg: aijhip_gamg_params_t fields; smoother: the GAMG level smoother,
         dict(type="richardson"|"chebyshev", its=, scale=, lo=, hi=) (gamg.mg_smoother;
         None: Richardson(1), scale 1); mat_vcycle: the widest block mat_solve and
         pc_mat_apply take with pc="gamg" (aijhip_ksp_set_mat_vcycle_width; 0: they
@@ -127,6 +133,19 @@ class KSPCG:
             self.set_mat_vcycle_width(mat_vcycle)
         if reuse_interpolation:
             self.reuse_interpolation = True
+        if ksp_type != "cg":
+            self.set_type(ksp_type)
+
+    def set_type(self, ksp_type):
+        """KSPSetType (aijhip_ksp_set_type): "cg", "bcgs" or the library's
+        integer code. The PC and its set-up stay."""
+        _pkg._check(_lib().aijhip_ksp_set_type(self._h, KSP_TYPES.get(ksp_type, ksp_type)))
+
+    @property
+    def ksp_type(self) -> str:
+        v = ctypes.c_int()
+        _pkg._check(_lib().aijhip_ksp_get_type(self._h, ctypes.byref(v)))
+        return {c: n for n, c in KSP_TYPES.items()}[v.value]
 
     @property
     def reuse_interpolation(self) -> bool:
@@ -380,6 +399,17 @@ class KSPCG:
             self.destroy()
         except Exception:
             pass
+
+
+class KSPBCGS(KSPCG):
+    """KSPBCGS on a SeqAIJHIP operator: preconditioned BiCGStab for nonsymmetric
+    operators (AIJHIP_KSP_BCGS), with KSPCG's interface. mat_solve raises the
+    library's error (the lock-step solver is CG); only norm="preconditioned"
+    solves."""
+
+    def __init__(self, A, *args, **kwargs):
+        kwargs["ksp_type"] = "bcgs"
+        super().__init__(A, *args, **kwargs)
 
 
 def bench_cg(pkg, A, nx, ny, nz, dev, iters=200):
